@@ -1,6 +1,7 @@
 """Benchmark of the flash-attention forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4] [--dump-outputs DIR]
+    python bench.py --full ...   (the headline, then everything else this file measures)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
     (`python bench.py --gpus N` with N > 1 and no launcher starts the N ranks itself, before
     any GPU work; fewer than N GPUs on the node, or a WORLD_SIZE that disagrees with --gpus,
@@ -12,9 +13,16 @@ d=128, bf16 storage / fp32 accumulate, synthetic N(0,1) inputs resident in HBM. 
 is one forward over the whole batch.  With N>1 every rank runs its own C3 batch (heads
 are independent units: weak scaling, no collective in the data path).
 
-Prints ONE JSON line on rank 0 with the metric, the MFMA roofline of the forward kernel
-(achieved = 4*B*H*L^2*d FLOPs per launch / average launch time from HIP events on the
-launch stream), a check of the headline output against fp64 attention on sampled heads, and
+Prints ONE JSON line on rank 0 with the metric, ms_per_step (the milliseconds one timed step
+took) and the MFMA roofline of the forward kernel (achieved = 4*B*H*L^2*d FLOPs per launch /
+average launch time from HIP events on the launch stream).  A plain run does only that: set
+up, settle the clock, --warmup untimed steps, exactly --steps timed ones, the line.
+--dump-outputs DIR also writes what the last timed step computed (DIR/out.npy, float32; the
+inputs are seeded, so two builds can be compared output for output).
+
+--full adds everything else: the measured MFMA ceiling (csrc/fa_probe.hip), a check of the
+headline output against fp64 attention on sampled heads, the per-variant extras (C2, the
+d-tiled shapes, C4 and its split plans, C5 split-KV over the ranks) and
 the CPU baseline: the oracle's restatement of the reference's
 flash_attention_v1/numpy_gpu_like_opt2.py (fp64, Bq=Bk=8) timed on k heads per usable host
 core, one head per process, extrapolated to the whole batch (and, beside it, the C/OpenMP
@@ -250,9 +258,10 @@ def clock_settle(torch, step, seconds):
     return time.perf_counter() - t0
 
 
-def c5_step(torch, fdist, dev, world, rank, impl="torch"):
+def c5_step(torch, fdist, dev, world, rank, impl="torch", keep=None):
     """One C5 split-KV step closure: the keys of B=32 H=8 L=16384 d=128 sharded over the
-    ranks, partial kernel -> all-to-all -> combine (dist.splitkv_attention)."""
+    ranks, partial kernel -> all-to-all -> combine (dist.splitkv_attention).  With a dict
+    `keep` each step leaves the tensor it returned in keep["out"] (--dump-outputs)."""
     cc = CONFIGS["c5"]
     B, H, L, d = cc["B"], cc["H"], cc["L"], cc["d"]
     lo, hi = fdist.shard_bounds(L, world, rank)
@@ -261,13 +270,19 @@ def c5_step(torch, fdist, dev, world, rank, impl="torch"):
     if impl == "native":
         comm = fdist.RcclComm()
 
-        def step():
-            fdist.splitkv_attention_native(q, k, v, comm)
+        def run():
+            return fdist.splitkv_attention_native(q, k, v, comm)
         kernel = ("fa_fwd_partial_ex per destination chunk + RCCL send/recv on the exchange stream + "
                   "fa_combine (C ABI fa_fwd_v2_dist; its launches are internal to libfa_mi355x_dist.so)")
     else:
+        def run():
+            return fdist.splitkv_attention(q, k, v)
+    if keep is None:
+        step = run
+    else:
         def step():
-            fdist.splitkv_attention(q, k, v)
+            keep["out"] = run()
+    if impl != "native":
         from exploring_flash_attention_amd import ops
         kernel = launched(ops, step)
         if world > 1:
@@ -451,6 +466,45 @@ def output_check(torch, q, k, v, out, n=16):
             "reference": "torch fp64 softmax(q k^T / sqrt(d)) v on the device, sampled heads incl. first/last"}
 
 
+DUMP_BYTES = 32 << 20  # --dump-outputs: float32 bytes written per run, all ranks together
+DUMP_SEED = 0
+
+
+def dump_heads(B, H, L, d, budget=DUMP_BYTES):
+    """The (b, h) heads of a [B, H, L, d] output that --dump-outputs writes: every head when
+    the whole output fits `budget` bytes of float32, else as many whole heads as fit, drawn
+    without replacement by a fixed seed (the same heads on every run), in batch order."""
+    import numpy as np
+    BH = B * H
+    n = max(1, min(BH, budget // max(1, L * d * 4)))
+    if n == BH:
+        return [(i // H, i % H) for i in range(BH)]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(BH, size=n, replace=False))
+    return [(int(i) // H, int(i) % H) for i in idx]
+
+
+def dump_outputs(torch, out, directory, world=1, rank=0):
+    """Write the tensor the timed path returned as float32 `<directory>/out.npy` (N > 1: each
+    rank its own out_rank<r>.npy, the byte budget shared): the whole tensor when it fits,
+    else the heads dump_heads picks, stacked [n, L, d].  Returns the record for the line."""
+    import numpy as np
+    B, H, L, d = out.shape
+    heads = dump_heads(B, H, L, d, DUMP_BYTES // world)
+    name = "out" if world == 1 else f"out_rank{rank}"
+    if len(heads) == B * H:
+        arr = out.float().cpu().numpy()
+        sample = "whole output [B, H, L, d]"
+    else:
+        flat = out.reshape(B * H, L, d)
+        sel = torch.tensor([b * H + h for b, h in heads], device=out.device)
+        arr = flat.index_select(0, sel).float().cpu().numpy()
+        sample = (f"{len(heads)} of the {B * H} heads [n, L, d], drawn by numpy default_rng({DUMP_SEED}) "
+                  f"(bench.dump_heads), batch order")
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return {"file": name + ".npy", "dtype": "float32", "shape": list(arr.shape), "sample": sample}
+
+
 def splitkv_scaling_field(c5, world):
     """The north_star's multi-GPU row (C5: one L=16384 batch's keys sharded over the ranks,
     partials exchanged over RCCL, combined per rank) lifted to the top of the line, so that the
@@ -519,7 +573,7 @@ def start_watchdog(seconds, rank, partial_line):
     return dog
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # The MI355X clock ramps up over the first ~50 ms of back-to-back launches (measured:
@@ -532,17 +586,25 @@ def main():
     ap.add_argument("--dist-impl", default="torch", choices=["torch", "native"],
                     help="splitkv-dist exchange: torch.distributed all_to_all, or the C ABI "
                          "fa_fwd_v2_dist (own RCCL communicator, grouped send/recv)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else: the CPU baselines, the "
+                         "per-variant extras (C2, d-tiled, C4, C5), the MFMA ceiling, the fp64 output check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as float32 DIR/out.npy (a fixed, "
+                         "seeded sample of heads where the output is larger than 32 MiB)")
     ap.add_argument("--cpu-cores", type=int, default=0, help="CPU baseline pool size (0 = the usable host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-variant extra timings")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the per-variant extra timings")
     ap.add_argument("--clock-warmup", type=float, default=0.25,
                     help="seconds of untimed headline steps right before --warmup (clock settle; 0 = off)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        sys.exit(self_launch(args.gpus, sys.argv[1:]))
+        sys.exit(self_launch(args.gpus, sys.argv[1:] if argv is None else list(argv)))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -555,7 +617,9 @@ def main():
     B, H, L, d = cfg["B"], cfg["H"], cfg["L"], cfg["d"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "heads":
+    cpu_legs = args.full and not args.no_cpu_baseline  # the CPU baselines
+    extras = args.full and not args.no_extra  # the per-variant timings and the C5 leg
+    if rank == 0 and world == 1 and cpu_legs and args.mode == "heads":
         ncores = args.cpu_cores or host_cores()[0]
         cpu = cpu_baseline(L, d, ncores)  # before any GPU initialisation (fork-safe)
         omp = cpu_baseline_openmp(L, d, ncores)
@@ -578,7 +642,7 @@ def main():
             dist.barrier()
 
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra and args.mode == "heads":
+    if rank == 0 and world == 1 and extras and args.mode == "heads":
         # the extras get a settled clock too (C3 forwards, untimed), then each its own warm-up
         cw = CONFIGS["c3"]
         qw, kw, vw = _make_inputs(torch, dev, cw["B"], cw["H"], cw["L"], cw["d"], seed=3)
@@ -614,20 +678,28 @@ def main():
         # untimed steps and exactly --steps timed ones.
         t_warm = clock_settle(torch, step, args.clock_warmup)
         wall, ev_ms = time_step(torch, step, args.steps, args.warmup, barrier)
-        ceiling = measured_ceiling(d) if rank == 0 else None  # after the timed window
+        result = out  # what ops.attention_v1 / attention_v2 hand back: the out= tensor
         work = flops(B, H, L, d)
         workload = ("FA-v1 fused / tiled-d forward (one kernel)" if cfg["variant"] == "v1"
                     else "FA-v2 split-KV forward")
         parallel = f"heads{world}" if world > 1 else "single"
-        if rank == 0:
-            check = output_check(torch, q, k, v, out)
     else:
         # C5: keys of one L=16384 sequence sharded over the ranks; all-to-all combine.
-        step, kernel, work = c5_step(torch, fdist, dev, world, rank, args.dist_impl)  # work: this rank's share
+        kept = {} if args.dump_outputs else None
+        step, kernel, work = c5_step(torch, fdist, dev, world, rank, args.dist_impl,
+                                     keep=kept)  # work: this rank's share
         t_warm = clock_settle(torch, step, min(args.clock_warmup, 0.1))
         wall, ev_ms = time_step(torch, step, args.steps, args.warmup, barrier)
+        result = kept["out"] if kept else None
         workload = "FA-v2 split-KV forward, keys sharded over ranks"
         parallel = f"kv{world}"
+
+    dumped = None
+    if args.dump_outputs:  # the last timed step's output, before anything else runs
+        dumped = dump_outputs(torch, result, args.dump_outputs, world, rank)
+    if rank == 0 and args.full and args.mode == "heads":
+        ceiling = measured_ceiling(d)  # after the timed window
+        check = output_check(torch, q, k, v, out)
 
     # max over ranks
     t = torch.tensor([wall, ev_ms], device=dev, dtype=torch.float64)
@@ -676,8 +748,10 @@ def main():
         if check is not None:
             line["check"] = check
         line["clock_warmup_s"] = round(t_warm, 3)
+        if dumped is not None:
+            line["outputs"] = dict(dumped, dir=args.dump_outputs)
     printed, dog = False, None
-    if not args.no_extra and args.mode == "heads":
+    if extras and args.mode == "heads":
         # C5 split-KV over all ranks (north_star: 1/2/4/8-GPU split-KV throughput and achieved
         # fraction); every rank takes part in the exchange, time = max over ranks.  A watchdog
         # keeps an exchange that never completes from costing the headline line: after

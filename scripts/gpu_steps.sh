@@ -16,7 +16,7 @@ for mode in "$@"; do
           > $OUT/tests.log 2>&1; rc=$?
       tail -3 $OUT/tests.log; echo "tests rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+      timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; rc=$?
       echo "bench rc=$rc"; head -c 600 $OUT/bench.json; echo; [ $rc -eq 0 ] || exit $rc ;;
     ab:*)  # ab:<config>:<lib1,lib2,...>
       IFS=: read -r _ cfg libs <<< "$mode"

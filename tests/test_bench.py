@@ -1,8 +1,12 @@
 """bench.py's host-side logic on CPU: the C5 watchdog fails the run, the head sample, the
-usable-core count."""
+usable-core count, the heads --dump-outputs writes; on the GPU, what a plain run does."""
+import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 from conftest import ROOT
 
@@ -136,3 +140,90 @@ def test_extra_traffic_records_are_labelled():
         assert tr["algorithmic_bytes"] == 8 * B * H * L * d
         assert tr["bytes_per_launch"] > 0 and tr["ratio"] > 0
         assert tr["kernel"] and tr["kernel"] != "(unlabelled)", name
+
+
+def test_dump_heads_are_fixed_and_fit_the_budget():
+    """--dump-outputs: the whole output where it fits 32 MiB of float32, else whole heads drawn
+    by a fixed seed -- the same ones on every call, distinct, in batch order, within the budget."""
+    import bench
+    assert bench.DUMP_BYTES <= 64_000_000
+    assert bench.dump_heads(2, 3, 200, 64) == [(b, h) for b in range(2) for h in range(3)]
+    for cfg in ("c2", "c3", "c4", "c5"):
+        c = bench.CONFIGS[cfg]
+        B, H, L, d = c["B"], c["H"], c["L"], c["d"]
+        hs = bench.dump_heads(B, H, L, d)
+        assert hs == bench.dump_heads(B, H, L, d) and hs == sorted(set(hs))
+        assert all(0 <= b < B and 0 <= h < H for b, h in hs)
+        assert len(hs) == min(B * H, bench.DUMP_BYTES // (L * d * 4)) >= 1
+    # N ranks share the budget
+    assert len(bench.dump_heads(32, 8, 1024, 128, bench.DUMP_BYTES // 8)) == 8
+
+
+def test_plain_and_full_arguments():
+    """--full and --dump-outputs exist, both off by default; --steps 0 is refused before any work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 2 and r.stdout == ""
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_its_output(gpu, tmp_path, capsys, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W`: exactly W + N forwards after the one
+    that names the kernel, none of the --full legs, one JSON line whose value follows from
+    ms_per_step; --dump-outputs writes the last step's output -- float32, under 64 MB, the same
+    bits on a second run, and the attention of the seeded inputs (bf16 build gate, test_gpu.GATE)."""
+    import torch
+
+    import bench
+    from exploring_flash_attention_amd import ops
+
+    def full_only(*a, **k):
+        raise AssertionError("a --full leg ran in a plain benchmark run")
+    for name in ("cpu_baseline", "cpu_baseline_openmp", "single_gpu_extras", "measured_ceiling", "output_check",
+                 "c5_step", "c5_breakdown"):
+        monkeypatch.setattr(bench, name, full_only)
+    calls = []
+    v1 = ops.attention_v1
+
+    def counted_v1(*a, **k):
+        calls.append(1)
+        return v1(*a, **k)
+    monkeypatch.setattr(ops, "attention_v1", counted_v1)
+    N, W = 3, 2
+    lines, outs = [], []
+    for sub in ("a", "b"):
+        del calls[:]
+        bench.main(["--gpus", "1", "--steps", str(N), "--warmup", str(W), "--clock-warmup", "0",
+                    "--dump-outputs", str(tmp_path / sub)])
+        assert len(calls) == 1 + W + N
+        printed = capsys.readouterr().out.strip().splitlines()
+        assert len(printed) == 1
+        lines.append(json.loads(printed[0]))
+        assert [f.name for f in (tmp_path / sub).iterdir()] == ["out.npy"]
+        outs.append(np.load(tmp_path / sub / "out.npy", allow_pickle=False))
+    c = bench.CONFIGS["c3"]
+    B, H, L, d = c["B"], c["H"], c["L"], c["d"]
+    for line in lines:
+        assert line["steps"] == N and line["warmup"] == W and line["n_gpus"] == 1
+        assert line["unit"] == "GFLOP/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+        assert line["metric"].startswith("flash-attn fwd GFLOP/s (B=32,H=8,L=1024,d=128")
+        assert line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(bench.flops(B, H, L, d) / (line["ms_per_step"] * 1e-3) / 1e9, rel=1e-3)
+        assert line["cpu_baseline"] is None and "extra" not in line and "check" not in line
+        assert "ceiling_measured" not in line["roofline"] and line["roofline"]["kernel"]
+        assert line["outputs"]["file"] == "out.npy" and line["outputs"]["dtype"] == "float32"
+    heads = bench.dump_heads(B, H, L, d)
+    a, b = outs
+    assert a.dtype == np.float32 and a.shape == (len(heads), L, d) and a.nbytes <= 64_000_000
+    assert np.array_equal(a, b)
+    q, k, v = bench._make_inputs(torch, gpu, B, H, L, d, seed=1234)
+    for i in (0, len(heads) // 2, len(heads) - 1):
+        bb, hh = heads[i]
+        qq, kk, vv = (t[bb, hh].double() for t in (q, k, v))
+        ref = (torch.softmax((qq @ kk.T) / d ** 0.5, dim=-1) @ vv).cpu().numpy()
+        err = np.abs(a[i] - ref)
+        big = np.abs(ref) > 1e-3
+        assert err.max() <= 6e-3 and (err[big] / np.abs(ref[big])).mean() <= 1e-2, (bb, hh, err.max())
