@@ -41,6 +41,7 @@ SIGNATURES = {
                                 ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "fa_fwd_v1": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P]),
     "fa_fwd_v1_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, ctypes.c_double, _I, _P]),
+    "fa_fwd_v1_causal": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_tiled_d": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
     "fa_fwd_v1_tiled_d_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, ctypes.c_double, _I, _P]),

@@ -452,6 +452,25 @@ int fa_fwd_v1_ex(const void* q, const void* k, const void* v, void* o, int64_t B
     return ok();
 }
 
+int fa_fwd_v1_causal(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
+                     int64_t L, int64_t d, double softmax_scale, int dtype, void* stream) {
+    fa::Elem e;
+    if (int st = check_shape(B, H, L, d, true)) return st;
+    if (wide_d(d))
+        return fail(FA_ERR_UNSUPPORTED, "causal: head dim d=%lld has no causal kernel (32, 64, 128, 256 only)",
+                    (long long)d);
+    if (int st = check_dtype(dtype, &e)) return st;
+    if (e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "causal: FA_DTYPE_FP64 has no causal kernel (bf16 / fp16 only)");
+    if (int st = check_ptrs(q, k, v, o)) return st;
+    fa::FwdArgs a = base_args(q, k, v, o, B * H, L, L, d, e);
+    if (int st = apply_scale(a, softmax_scale)) return st;
+    kernels_begin();
+    if (hipError_t he = fa::launch_fwd_causal(e, (int)d, a, (hipStream_t)stream))
+        return hip_fail(he, "fa_fwd_v1_causal launch");
+    return ok();
+}
+
 int fa_fwd_v1_tiled_d(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
                       int64_t L, int64_t d, int d_tile_qk, int d_tile_v, int dtype, void* stream) {
     return fa_fwd_v1_tiled_d_scaled(q, k, v, o, B, H, L, d, d_tile_qk, d_tile_v,

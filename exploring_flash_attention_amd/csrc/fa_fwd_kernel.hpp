@@ -1,5 +1,6 @@
 // fa_fwd_kernel.hpp -- flash-attention forward kernel for MI355X (gfx950 / CDNA4), included by
-// fa_fwd.hip (contiguous [B,H,L,d] launches) and fa_fwd_strided.hip (strided launches).
+// fa_fwd.hip (contiguous [B,H,L,d] launches), fa_fwd_strided.hip (strided launches) and
+// fa_fwd_causal.hip (the causal instantiations).
 //
 // One kernel template serves the three reference kernel families:
 //   final mode   (MODE=kFinal): FA-v1 fused / d-tiled forward
@@ -99,8 +100,13 @@ namespace fa {
 // STRIDED: Q, K, V and O addressed through per-tensor (batch, head, row) strides in elements
 // (d contiguous, K and V sharing strides), e.g. [B, L, H, d] tensors viewed as [B, H, L, d];
 // false (contiguous [B, H, L, d]) folds every stride to a constant.
-template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false>
+// CAUSAL (final mode, contiguous, Lq = Lk; instantiated in fa_fwd_causal.hip): query row i sees
+// keys 0..i.  A workgroup's key range ends at its query tile's diagonal, the tiles that cross
+// the diagonal are masked per element under a compile-time step flag (CMNEXT below), and the
+// query tiles of a head are handed out longest first.  Everything else is the non-causal kernel.
+template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false>
 __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void fa_fwd_kernel(FwdArgs a) {
+    static_assert(!CAUSAL || (MODE == kFinal && !STRIDED), "causal: final mode, contiguous tensors");
     using M = Mma<T>;
     using v8 = typename M::v8;
     constexpr int RB = kRB;                   // 32-row query blocks per wave
@@ -125,7 +131,16 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int w = xcd_remap(blockIdx.x, gridDim.x);
     int qt, split;
     int64_t bh;
-    decode_item(a, w, qt, split, bh);
+    if constexpr (CAUSAL) {
+        // Query tile qt walks qt + 1 times as many KV tiles as tile 0: within a head the long
+        // ones go first (work items are dispatched in w order), so that the launch ends on
+        // short workgroups.  Still a bijection onto (query tile, b*h), a head's tiles adjacent.
+        qt = a.nqt - 1 - w % a.nqt;
+        split = 0;
+        bh = w / a.nqt;
+    } else {
+        decode_item(a, w, qt, split, bh);
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -142,7 +157,10 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     FA_STAMP_V(6, __builtin_amdgcn_s_getreg(4 | (31 << 11)));   // HW_REG_HW_ID, 32 bits
     FA_STAMP_V(7, __builtin_amdgcn_s_getreg(20 | (31 << 11)));  // HW_REG_XCC_ID
     const int64_t kv_begin = (int64_t)split * a.kv_per_split;
-    const int64_t kv_end = kv_begin + a.kv_per_split < a.Lk ? kv_begin + a.kv_per_split : a.Lk;
+    // (causal: the keys up to the query tile's last row -- a multiple of the KV tile unless it
+    // is Lk itself, where the partial-last-tile path applies as ever)
+    const int64_t kv_end = CAUSAL ? ((int64_t)(qt + 1) * kBQ < a.Lk ? (int64_t)(qt + 1) * kBQ : a.Lk)
+                           : kv_begin + a.kv_per_split < a.Lk ? kv_begin + a.kv_per_split : a.Lk;
     const int nkv = (int)(kv_end - kv_begin);
     const int ntiles = (nkv + kBK - 1) / kBK;
 
@@ -345,6 +363,27 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
                 }
         }
     };
+    // causal: keys above the lane's query row -> -inf, in a tile that crosses the diagonal (the
+    // last kBQ / kBK tiles of the workgroup's range; the key tail can only be among them and
+    // is folded into the same bound).  A tile may be wholly masked for a wave (wave 0 against
+    // keys 64.. of its own query tile): its row max is then -inf for every row, the rescale
+    // test mx > m + kThr is false and every P is 2^(-inf - m) = 0 with m finite -- tile 0 holds
+    // key 0, which every row sees, so m is finite from the prologue on.
+    auto cmask = [&](int t, f32x16 (&s)[RB][NKB]) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            int last = (int)q_row0 + 32 * r;  // last visible key of this lane's row
+            if constexpr (TAIL) last = last < nkv - 1 ? last : nkv - 1;
+            const int lim = last - t * kBK;   // ... relative to the tile
+#pragma unroll
+            for (int b2 = 0; b2 < NKB; ++b2)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int key = b2 * 32 + (i & 3) + 8 * (i >> 2) + 4 * hf;
+                    if (key > lim) s[r][b2][i] = -INFINITY;
+                }
+        }
+    };
     // row max of a (masked) tile, both lane halves, in log2 units (v_maximum3: no
     // canonicalising v_max x,x per MFMA result, unlike fmaxf)
     auto rowmax = [&](const f32x16 (&s)[RB][NKB], float (&mx)[RB]) {
@@ -404,8 +443,11 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         //   MORE      tile t+1 exists
         //   MASKNEXT  tile t+1 may be the partial last tile (needs the key mask)
         //   DMAK      tile t+2 exists (its K is prefetched now)
+        //   CMNEXT    (causal) tile t+1 crosses the diagonal: the per-element causal mask, which
+        //             covers the key tail too.  Tiles below the diagonal run the unmasked steps.
         constexpr int F = decltype(flags_c)::value;
         constexpr bool MORE = F & 1, MASKNEXT = TAIL && (F & 2), DMAK = F & 4;
+        constexpr bool CMNEXT = CAUSAL && (F & 8);
 
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
@@ -471,7 +513,8 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         });
         if constexpr (MORE) {
             if constexpr ((kRowmaxFenceMask & d_bit(D)) != 0) __builtin_amdgcn_sched_barrier(0);
-            if constexpr (MASKNEXT) mask(t + 1, sn);
+            if constexpr (CMNEXT) cmask(t + 1, sn);
+            else if constexpr (MASKNEXT) mask(t + 1, sn);
             rowmax(sn, mx);
         }
         __syncthreads();  // hipcc drains the DMA (vmcnt(0)) here: K(t+2), V(t+1) landed
@@ -644,7 +687,12 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     f32x16 sa[RB][NKB], sb[RB][NKB];
     float mx[RB];
     qk(kring, sa);
-    if constexpr (TAIL) mask(0, sa);
+    // (causal: the first KV tile that crosses the diagonal; tile 0 does only in query tile 0)
+    constexpr int ND = kBQ / kBK;
+    const int td0 = CAUSAL ? qt * ND : 0;
+    if constexpr (CAUSAL) {
+        if (td0 == 0) cmask(0, sa);
+    } else if constexpr (TAIL) mask(0, sa);
     rowmax(sa, mx);
     // the reference max starts at tile 0's row max (every tile holds a valid key): step 0
     // then never takes the rescale branch that a -inf start would force on every workgroup
@@ -656,30 +704,61 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     {
         using C0 = std::integral_constant<int, 0>;
         using C1 = std::integral_constant<int, 1>;
-        // flags: 1 = MORE, 2 = MASKNEXT, 4 = DMAK (see step)
+        // flags: 1 = MORE, 2 = MASKNEXT, 4 = DMAK, 8 = CMNEXT (see step)
         using STEADY = std::integral_constant<int, 1 | 4>;     // t+1, t+2 exist, t+1 not last
         using NEXTLAST = std::integral_constant<int, 1 | 2>;   // t+1 is the last tile
         using NEXTLASTK = std::integral_constant<int, 1 | 2 | 4>;
         using LAST = std::integral_constant<int, 0>;
-        // (the pinned schedule for every step with a next tile; the last step has no QK^T)
+        // (the pinned schedule for every step with a next, unmasked tile; the last step has no
+        // QK^T, and the pinned step has no room for the causal mask)
         auto run = [&](auto par_c, auto flags_c, int t, f32x16 (&sc)[RB][NKB], f32x16 (&sn)[RB][NKB],
                        float (&mx)[RB]) {
-            if constexpr (PIN && (decltype(flags_c)::value & 1)) step_pinned(par_c, flags_c, t, sc, sn, mx);
+            if constexpr (PIN && (decltype(flags_c)::value & 9) == 1) step_pinned(par_c, flags_c, t, sc, sn, mx);
             else step(par_c, flags_c, t, sc, sn, mx);
         };
         int t = 0;
-        for (; t + 2 < ntiles; t += 2) {
-            // step t: tile t+1 is never the last one here.  Step t+1 may prefetch K(t+3)
-            // past the end: the buffer range check turns it into zeros nobody reads, which
-            // keeps the step branch-free.
-            run(C0{}, STEADY{}, t, sa, sb, mx);
-            run(C1{}, NEXTLASTK{}, t + 1, sb, sa, mx);
-        }
-        if (ntiles - t == 2) {  // t is even here
-            run(C0{}, NEXTLAST{}, t, sa, sb, mx);
-            run(C1{}, LAST{}, t + 1, sb, sa, mx);
+        if constexpr (CAUSAL) {
+            // Tiles 0 .. td0-1 lie below the diagonal (td0 is even): the steady, unmasked pair
+            // (the pinned one at d = 128) up to the step whose next tile is td0; then the 1 to ND
+            // tiles that cross the diagonal, each masked by the step before it.  (K prefetched
+            // past the end: zeros nobody reads, as below.)
+            using CNEXTK = std::integral_constant<int, 1 | 4 | 8>;
+            using CNEXT = std::integral_constant<int, 1 | 8>;
+            for (; t + 2 < td0; t += 2) {
+                run(C0{}, STEADY{}, t, sa, sb, mx);
+                run(C1{}, STEADY{}, t + 1, sb, sa, mx);
+            }
+            if (td0 > 0) {
+                run(C0{}, STEADY{}, t, sa, sb, mx);
+                run(C1{}, CNEXTK{}, t + 1, sb, sa, mx);
+                t += 2;
+            }
+            if constexpr (ND > 2) {
+                for (; t + 2 < ntiles; t += 2) {
+                    run(C0{}, CNEXTK{}, t, sa, sb, mx);
+                    run(C1{}, CNEXTK{}, t + 1, sb, sa, mx);
+                }
+            }
+            if (ntiles - t == 2) {
+                run(C0{}, CNEXT{}, t, sa, sb, mx);
+                run(C1{}, LAST{}, t + 1, sb, sa, mx);
+            } else {
+                run(C0{}, LAST{}, t, sa, sb, mx);
+            }
         } else {
-            run(C0{}, LAST{}, t, sa, sb, mx);
+            for (; t + 2 < ntiles; t += 2) {
+                // step t: tile t+1 is never the last one here.  Step t+1 may prefetch K(t+3)
+                // past the end: the buffer range check turns it into zeros nobody reads, which
+                // keeps the step branch-free.
+                run(C0{}, STEADY{}, t, sa, sb, mx);
+                run(C1{}, NEXTLASTK{}, t + 1, sb, sa, mx);
+            }
+            if (ntiles - t == 2) {  // t is even here
+                run(C0{}, NEXTLAST{}, t, sa, sb, mx);
+                run(C1{}, LAST{}, t + 1, sb, sa, mx);
+            } else {
+                run(C0{}, LAST{}, t, sa, sb, mx);
+            }
         }
     }
 

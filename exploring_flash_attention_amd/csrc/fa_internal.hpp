@@ -133,6 +133,8 @@ hipError_t launch_fwd(Elem t, Elem pt, int d, Mode mode, const FwdArgs& a, hipSt
 hipError_t launch_combine(Elem t, Elem pt, int d, const CombineArgs& a, hipStream_t s);
 // the strided instantiations (fa_fwd_strided.hip); launch_fwd forwards there when a.strided
 hipError_t launch_fwd_strided(Elem t, Elem pt, int d, Mode mode, const FwdArgs& a, hipStream_t s);
+// the causal forward (fa_fwd_causal.hip): final mode, contiguous, Lq = Lk, one split, bf16 / fp16
+hipError_t launch_fwd_causal(Elem t, int d, const FwdArgs& a, hipStream_t s);
 int fwd_lds_bytes(int d);
 // compute units of the device that owns `s` (the current device for the null stream;
 // fa_capi.cpp; 256 without a device)

@@ -174,13 +174,41 @@ def _out(out, q, shape=None, dtype=None, strided=False):
     return out
 
 
-def attention_v1(q, k, v, out=None):
+def _attention_v1_causal(q, k, v, o):
+    """attention_v1(causal=True) after the common checks: fa_fwd_v1_causal on contiguous
+    tensors of a kernel head dim, zero-padded or copied to that form otherwise."""
+    B, H, L, d = q.shape
+    if q.dtype == torch.float64:
+        raise NotImplementedError("causal attention: float64 tensors are not supported (the fp64 kernels "
+                                  "have no causal mode; use bfloat16 or float16)")
+    if d > 256:
+        raise NotImplementedError(f"causal attention: head dim d={d} is not supported (1 <= d <= 256; the "
+                                  "d-tiled kernels for d = 384 / 512 have no causal mode)")
+    D = kernel_head_dim(d)
+    if q.numel() == 0:
+        return o
+    if not all(t.is_contiguous() for t in (q, k, v, o)):  # no strided causal kernel
+        return _via_contiguous(attention_v1, q, k, v, o, causal=True)
+    qp, kp, vp = (_pad_d(t, D) for t in (q, k, v))
+    op = o if D == d else torch.empty((B, H, L, D), dtype=q.dtype, device=q.device)
+    _launched(lib().fa_fwd_v1_causal(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(op), B, H, L, D, 1.0 / d ** 0.5,
+                                     _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
+
+
+def attention_v1(q, k, v, out=None, causal=False):
     """FA-v1 fused forward: O = softmax(q k^T / sqrt(d)) v.  Any 1 <= d <= 256 (head dims
     without a kernel are zero-padded to the next one, see kernel_head_dim).  q, k, v and out
     may be strided [B, H, L, d] views with a contiguous d -- e.g. ``x.transpose(1, 2)`` of a
-    [B, L, H, d] tensor -- which the kernel addresses in place (fa_fwd_v1_ex)."""
+    [B, L, H, d] tensor -- which the kernel addresses in place (fa_fwd_v1_ex).
+
+    ``causal=True``: row i attends to keys 0..i only (fa_fwd_v1_causal; bfloat16 / float16,
+    d <= 256 -- float64 and wider head dims raise NotImplementedError; strided views are
+    copied to contiguous tensors first)."""
     _check_qkv(q, k, v, strided=True)
     o = _out(out, q, strided=True)
+    if causal:
+        return _attention_v1_causal(q, k, v, o)
     B, H, L, d = q.shape
     D = kernel_head_dim(d)
     if q.numel() == 0:  # no rows: nothing to launch (the reference returns an empty O)

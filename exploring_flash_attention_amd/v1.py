@@ -17,7 +17,10 @@ Reference surfaces mirrored (tyler-utah/exploring_flash_attention):
 the gfx950 kernel uses its own tiles (128 query rows x 64 keys, see
 ``ops.kernel_geometry``) -- the result does not depend on them.
 """
+import functools
+
 import numpy as np
+import torch
 
 from . import _host, ops
 
@@ -58,15 +61,24 @@ def flash_attention_tiled(Q, K, V, *args, Bq=8, Bk=8, **kw):
     return _run_host(Q, K, V)
 
 
-def flash_attention_v1(Q, K, V, O=None, B=None, H=None, L=None, d=None):
+def flash_attention_v1(Q, K, V, O=None, B=None, H=None, L=None, d=None, causal=False):
     """``flash_attention_v1(Q, K, V) -> O`` (host or device), or the launcher form
     ``flash_attention_v1(Q, K, V, O, B, H, L, d)``: O[B,H,L,d] written in place,
-    asynchronous on the current stream."""
+    asynchronous on the current stream.
+
+    ``causal=True`` (not in the reference): row i attends to keys 0..i, see
+    ``ops.attention_v1``.  bf16 / fp16 only: host arrays other than float16 would run the
+    fp64 kernels, which have no causal mode, and raise NotImplementedError."""
     if O is None:
-        return _host.run_qkv(ops.attention_v1, Q, K, V)
+        if not causal:
+            return _host.run_qkv(ops.attention_v1, Q, K, V)
+        if not _host.is_device_tensor(Q) and _host.compute_dtype(*(np.asarray(x) for x in (Q, K, V))) == torch.float64:
+            raise NotImplementedError("causal attention: float32 / float64 host arrays run the float64 kernels, "
+                                      "which have no causal mode (pass float16 arrays or bf16 / fp16 device tensors)")
+        return _host.run_qkv(functools.partial(ops.attention_v1, causal=True), Q, K, V)
     assert B > 0 and H > 0 and L > 0 and d > 0, "All dimensions must be positive"
     assert tuple(Q.shape) == (B, H, L, d), f"Q shape {tuple(Q.shape)} != {(B, H, L, d)}"
-    ops.attention_v1(Q, K, V, out=O)
+    ops.attention_v1(Q, K, V, out=O, causal=causal)
 
 
 flash_attention_v1_opt1 = flash_attention_v1

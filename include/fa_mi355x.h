@@ -2,8 +2,10 @@
  * fa_mi355x.h -- C ABI of the MI355X (gfx950) flash-attention forward library
  * (libfa_mi355x.so, built from exploring_flash_attention_amd/csrc/).
  *
- * Computes the exact, non-causal attention forward O = softmax(Q K^T / sqrt(d)) V
- * over contiguous row-major [B, H, L, d] tensors held in device memory (HBM).
+ * Computes the exact attention forward O = softmax(Q K^T / sqrt(d)) V over contiguous
+ * row-major [B, H, L, d] tensors held in device memory (HBM): non-causal (every query row
+ * attends to every key) in all entry points but fa_fwd_v1_causal, which masks row i to keys
+ * 0..i (the reference has no causal mode).
  * All entry points are asynchronous on the caller's HIP stream (pass NULL for the
  * null stream), never allocate, never synchronise the device, and return an
  * fa_status_t.  On failure fa_last_error() returns a thread-local message.
@@ -79,7 +81,9 @@ typedef enum fa_dtype {
  *          (inserted before workspace / dtype), fa_fwd_v2_workspace_size_ex was added;
  *   0.3 -- head dims 384 and 512 (the d-tiled kernels: fa_fwd_v1, fa_fwd_v1_tiled_d, and
  *          fa_fwd_v2 unsplit), fa_fwd_v1_tiled_d_scaled added;
- *   0.4 -- fa_last_kernels and fa_fwd_v2_ex2 (FA_V2_COUNTERS_ZERO) added (no signature changed).
+ *   0.4 -- fa_last_kernels and fa_fwd_v2_ex2 (FA_V2_COUNTERS_ZERO) added (no signature changed);
+ *          fa_fwd_v1_causal added later under the same number (an addition only: callers built
+ *          against 0.4 stay valid; a library without it fails to resolve the symbol).
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -119,6 +123,17 @@ int fa_fwd_v1(const void* q, const void* k, const void* v, void* o,
  * d (e.g. flash_attention_v1/numpy_gpu_like_opt2.py:198 with d = 16); the Python layer
  * (exploring_flash_attention_amd/ops.py) does exactly this. */
 int fa_fwd_v1_scaled(const void* q, const void* k, const void* v, void* o,
+                     int64_t B, int64_t H, int64_t L, int64_t d, double softmax_scale,
+                     int dtype, void* stream);
+/* fa_fwd_v1_scaled with a causal mask: row i attends to keys 0..i (top-left aligned; query
+ * and key length are both L), O[i] = softmax(softmax_scale * Q[i] K[0..i]^T) V[0..i].  Every
+ * row sees key 0, so no row is empty.  Contiguous [B, H, L, d], FA_DTYPE_BF16 or FA_DTYPE_FP16,
+ * d in {32, 64, 128, 256}; d = 384 / 512 and FA_DTYPE_FP64 return FA_ERR_UNSUPPORTED (the
+ * message names "causal").  Pointer, size and scale checks as fa_fwd_v1_scaled.  A query tile
+ * of 128 rows walks only the keys up to its last row, so a long sequence does about half the
+ * work of fa_fwd_v1.  fa_last_kernels: "fa_fwd_kernel<final, causal>".  The split-KV, d-tiled,
+ * strided and multi-GPU entry points have no causal form. */
+int fa_fwd_v1_causal(const void* q, const void* k, const void* v, void* o,
                      int64_t B, int64_t H, int64_t L, int64_t d, double softmax_scale,
                      int dtype, void* stream);
 /* fa_fwd_v1_scaled on strided tensors.  q_strides, kv_strides (shared by k and v) and
