@@ -7,7 +7,8 @@ hand-written CDNA4 HIP kernels behind a C ABI (include/fa_mi355x.h,
 ``_lib/libfa_mi355x.so``).  ``ops`` has the zero-copy device-tensor operators and
 ``dist`` the split-KV forward sharded over the GPUs of a node with RCCL.
 ``attention_v1`` / ``flash_attention_v1`` take ``causal=True`` (row i attends to keys 0..i;
-bf16 / fp16, d <= 256); every other surface is non-causal, as the reference is.
+bf16 / fp16, d <= 256) and grouped-query K / V (``[B, H_kv, L, d]`` with H a multiple of H_kv;
+same types and head dims); every other surface is non-causal with H_kv = H, as the reference is.
 
 There is no CPU fallback: every entry point raises if the HIP library is not built or no
 ROCm device is present.

@@ -471,6 +471,34 @@ int fa_fwd_v1_causal(const void* q, const void* k, const void* v, void* o, int64
     return ok();
 }
 
+int fa_fwd_v1_gqa(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H, int64_t H_kv,
+                  int64_t L, int64_t d, double softmax_scale, unsigned flags, int dtype, void* stream) {
+    fa::Elem e;
+    if (flags & ~FA_FWD_CAUSAL)
+        return fail(FA_ERR_INVALID_ARG, "unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
+    const bool causal = (flags & FA_FWD_CAUSAL) != 0;
+    if (int st = check_shape(B, H, L, d, true)) return st;
+    if (H_kv <= 0 || H_kv > H || H % H_kv != 0)
+        return fail(FA_ERR_INVALID_ARG, "H_kv=%lld must be positive and divide H=%lld", (long long)H_kv, (long long)H);
+    if (H_kv == H)  // every head its own K/V: the MHA entry points, their kernels and labels
+        return causal ? fa_fwd_v1_causal(q, k, v, o, B, H, L, d, softmax_scale, dtype, stream)
+                      : fa_fwd_v1_scaled(q, k, v, o, B, H, L, d, softmax_scale, dtype, stream);
+    if (wide_d(d))
+        return fail(FA_ERR_UNSUPPORTED, "gqa: head dim d=%lld has no GQA kernel (32, 64, 128, 256 only)", (long long)d);
+    if (int st = check_dtype(dtype, &e)) return st;
+    if (e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "gqa: FA_DTYPE_FP64 has no GQA kernel (bf16 / fp16 only)");
+    if (int st = check_ptrs(q, k, v, o)) return st;
+    fa::FwdArgs a = base_args(q, k, v, o, B * H, L, L, d, e);
+    if (int st = apply_scale(a, softmax_scale)) return st;
+    a.H = H;
+    a.kv_group = (int)(H / H_kv);
+    kernels_begin();
+    if (hipError_t he = fa::launch_fwd_gqa(e, (int)d, causal, a, (hipStream_t)stream))
+        return hip_fail(he, "fa_fwd_v1_gqa launch");
+    return ok();
+}
+
 int fa_fwd_v1_tiled_d(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
                       int64_t L, int64_t d, int d_tile_qk, int d_tile_v, int dtype, void* stream) {
     return fa_fwd_v1_tiled_d_scaled(q, k, v, o, B, H, L, d, d_tile_qk, d_tile_v,

@@ -57,9 +57,12 @@ namespace fa {
 // block per workgroup) 3285 -> 3002 us.  The first version -- (tile, block) items chained in
 // decode order with the last arriver combining in the middle of its chain -- lost 4-10x: the
 // combine's serial loads under full register pressure.
-template <typename T, int MODE>
+// GQA (final mode; fa_fwd_gqa.hip): an item's K / V base is that of head b*h / a.kv_group --
+// nothing else of an item, and nothing inside a step, changes.
+template <typename T, int MODE, bool GQA = false>
 __global__ __launch_bounds__(kThreads, 2) void fa_fwd16_chain_kernel(FwdArgs a, int nitems) {
     static_assert(MODE == kFinal || MODE == kFused, "chain modes");
+    static_assert(!GQA || MODE == kFinal, "GQA: final mode");
     constexpr bool FUSED = MODE == kFused;
     using M = Mma<T>;
     using v8 = typename M::v8;
@@ -115,12 +118,20 @@ __global__ __launch_bounds__(kThreads, 2) void fa_fwd16_chain_kernel(FwdArgs a, 
     };
     auto item = [&](int j) {  // query tile w of this workgroup's list (fused: its split 0)
         const int w = __builtin_amdgcn_readfirstlane(gstart + l + nl * j);
-        const int qt = w % a.nqt;
-        const int64_t bh = w / a.nqt;
+        int qt;
+        int64_t bh, kvh;
+        if constexpr (GQA) {
+            decode_item_gqa<false>(a, w, qt, bh);
+            kvh = gqa_kv_head(a, bh);
+        } else {
+            qt = w % a.nqt;
+            bh = w / a.nqt;
+            kvh = bh;
+        }
         const int64_t q0 = (int64_t)qt * kBQ;
         Item it;
-        it.k = uni((const unsigned short*)a.k + bh * a.Lk * D);
-        it.v = uni((const unsigned short*)a.v + bh * a.Lk * D);
+        it.k = uni((const unsigned short*)a.k + kvh * a.Lk * D);
+        it.v = uni((const unsigned short*)a.v + kvh * a.Lk * D);
         it.grp = bh * a.nqt + qt;
         it.blk = it.grp;
         it.q = uni((const unsigned short*)a.q + (bh * a.Lq + q0) * D);

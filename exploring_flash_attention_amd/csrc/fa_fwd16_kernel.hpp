@@ -54,11 +54,13 @@ struct NoHook {
 // One work item (query tile, split, b*h) of the kernel; `at_loop_end` runs once, right after
 // the KV loop's last barrier (round 4's dynamic-claim experiment claimed its next item there;
 // measured and removed).
-template <typename T, typename PT, int D, int MODE, bool STR = false, typename Hook = NoHook>
+// GQA (final mode, contiguous; fa_fwd_gqa.hip): K / V head b*h / a.kv_group, as fa_fwd_kernel.
+template <typename T, typename PT, int D, int MODE, bool STR = false, typename Hook = NoHook, bool GQA = false>
 __device__ __forceinline__ void fa_fwd16_item(const FwdArgs& a, const int w, const Hook& at_loop_end = Hook{}) {
     using M = Mma<T>;
     using v8 = typename M::v8;
     static_assert(D == 128, "16x16x32 kernel: d = 128");
+    static_assert(!GQA || (MODE == kFinal && !STR), "GQA: final mode, contiguous tensors");
     constexpr int ROWB = D * 2;        // bytes per LDS row
     constexpr int kBK = 64;            // keys per KV tile
     constexpr int TILEB = kBK * ROWB;  // bytes of one K (or V) tile image
@@ -81,7 +83,12 @@ __device__ __forceinline__ void fa_fwd16_item(const FwdArgs& a, const int w, con
 
     int qt, split;
     int64_t bh;
-    decode_item(a, w, qt, split, bh);
+    if constexpr (GQA) {
+        decode_item_gqa<false>(a, w, qt, bh);
+        split = 0;
+    } else {
+        decode_item(a, w, qt, split, bh);
+    }
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,7 +108,8 @@ __device__ __forceinline__ void fa_fwd16_item(const FwdArgs& a, const int w, con
     const int krb = STR ? (int)(a.k_stride[2] * 2) : ROWB;
     const int64_t hb = STR ? bh / a.H : 0, hh = STR ? bh - hb * a.H : 0;
     const int64_t q_head = STR ? hb * a.q_stride[0] + hh * a.q_stride[1] : bh * a.Lq * D;
-    const int64_t k_head = STR ? hb * a.k_stride[0] + hh * a.k_stride[1] : bh * a.Lk * D;
+    int64_t k_head = STR ? hb * a.k_stride[0] + hh * a.k_stride[1] : bh * a.Lk * D;
+    if constexpr (GQA) k_head = gqa_kv_head(a, bh) * a.Lk * D;
     const int64_t o_head = STR ? hb * a.o_stride[0] + hh * a.o_stride[1] : bh * a.Lq * D;
     const int64_t orow = STR ? a.o_stride[2] : D;
     const unsigned short* Qh = (const unsigned short*)a.q + q_head + q_tile0 * (qrb / 2);
@@ -745,9 +753,9 @@ __device__ __forceinline__ void fa_fwd16_item(const FwdArgs& a, const int w, con
     }
 }
 
-template <typename T, typename PT, int D, int MODE, bool STR = false>
+template <typename T, typename PT, int D, int MODE, bool STR = false, bool GQA = false>
 __global__ __launch_bounds__(kThreads, 2) void fa_fwd16_kernel(FwdArgs a) {
-    fa_fwd16_item<T, PT, D, MODE, STR>(a, xcd_remap(blockIdx.x, gridDim.x));
+    fa_fwd16_item<T, PT, D, MODE, STR, NoHook, GQA>(a, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 }  // namespace fa

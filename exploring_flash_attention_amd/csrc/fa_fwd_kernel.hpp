@@ -104,9 +104,13 @@ namespace fa {
 // keys 0..i.  A workgroup's key range ends at its query tile's diagonal, the tiles that cross
 // the diagonal are masked per element under a compile-time step flag (CMNEXT below), and the
 // query tiles of a head are handed out longest first.  Everything else is the non-causal kernel.
-template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false>
+// GQA (final mode, contiguous, causal or not; instantiated in fa_fwd_gqa.hip): K and V hold
+// BH / a.kv_group heads and query head b*h reads head b*h / kv_group -- only the K / V base moves.
+template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false,
+          bool GQA = false>
 __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void fa_fwd_kernel(FwdArgs a) {
     static_assert(!CAUSAL || (MODE == kFinal && !STRIDED), "causal: final mode, contiguous tensors");
+    static_assert(!GQA || (MODE == kFinal && !STRIDED), "GQA: final mode, contiguous tensors");
     using M = Mma<T>;
     using v8 = typename M::v8;
     constexpr int RB = kRB;                   // 32-row query blocks per wave
@@ -131,7 +135,10 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int w = xcd_remap(blockIdx.x, gridDim.x);
     int qt, split;
     int64_t bh;
-    if constexpr (CAUSAL) {
+    if constexpr (GQA) {
+        decode_item_gqa<CAUSAL>(a, w, qt, bh);
+        split = 0;
+    } else if constexpr (CAUSAL) {
         // Query tile qt walks qt + 1 times as many KV tiles as tile 0: within a head the long
         // ones go first (work items are dispatched in w order), so that the launch ends on
         // short workgroups.  Still a bijection onto (query tile, b*h), a head's tiles adjacent.
@@ -169,7 +176,8 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int krb = STRIDED ? (int)(a.k_stride[2] * 2) : ROWB;
     const int64_t hb = STRIDED ? bh / a.H : 0, hh = STRIDED ? bh - hb * a.H : 0;
     const int64_t q_head = STRIDED ? hb * a.q_stride[0] + hh * a.q_stride[1] : bh * a.Lq * D;
-    const int64_t k_head = STRIDED ? hb * a.k_stride[0] + hh * a.k_stride[1] : bh * a.Lk * D;
+    int64_t k_head = STRIDED ? hb * a.k_stride[0] + hh * a.k_stride[1] : bh * a.Lk * D;
+    if constexpr (GQA) k_head = gqa_kv_head(a, bh) * a.Lk * D;
     // Q descriptor over this workgroup's query tile only, so that its 32-bit offsets stay
     // small however long the sequence (rows past Lq read zeros)
     const int64_t q_tile0 = (int64_t)qt * kBQ;

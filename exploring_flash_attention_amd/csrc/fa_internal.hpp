@@ -73,6 +73,10 @@ struct FwdArgs {
     // (batch, head, row); d is contiguous and V shares K's strides.  strided == 0: contiguous
     // [B, H, L, d] and these are unused.
     int strided;
+    // GQA (fa_fwd_gqa.hip; final mode, contiguous, one split): G = H / H_kv query heads share a
+    // K/V head, k and v are [B*H_kv][Lk][D] and query head b*H + h reads K/V head (b*H + h) / G.
+    // 0 or 1: every head its own K/V.  (It fills the padding in front of H: no field moved.)
+    int kv_group;
     int64_t H;
     int64_t q_stride[3], k_stride[3], o_stride[3];
     // d-tiled kernels (d = 384 / 512): effective column chunks of K and V (32, 64 or 128)
@@ -112,6 +116,30 @@ __device__ __forceinline__ void decode_item(const FwdArgs& a, int w, int& qt, in
     }
 }
 
+// GQA: the K/V head of flat query head bh (below 2^31: it is decoded from a 32-bit work item)
+__device__ __forceinline__ int64_t gqa_kv_head(const FwdArgs& a, int64_t bh) {
+    return (int64_t)((unsigned)bh / (unsigned)a.kv_group);
+}
+// GQA work order of item w (after xcd_remap), both measured on both kernels (DESIGN.md section
+// 3.5, profiles/gqa_order_ab.json).  Non-causal: (b*h, query tile), the MHA order -- a group's
+// heads are adjacent in b*h and share their K / V in L2 as a head's query tiles do; the
+// group-fastest order measured within the windows' spread of it.  Causal: (K/V head, query tile
+// longest first, head in group) -- the G workgroups that walk the same keys of the same K/V
+// head, and are equally long, are neighbours: 4.6 % (B4 H32 H_kv8 L4096) and 6.6 % (B32 H8
+// H_kv2 L1024) faster than the MHA order.  Both are bijections onto (b*h, query tile).
+template <bool CAUSAL>
+__device__ __forceinline__ void decode_item_gqa(const FwdArgs& a, int w, int& qt, int64_t& bh) {
+    if constexpr (CAUSAL) {
+        const int G = a.kv_group;
+        const int g = w % G, rest = w / G;
+        qt = a.nqt - 1 - rest % a.nqt;
+        bh = (int64_t)(rest / a.nqt) * G + g;
+    } else {
+        qt = w % a.nqt;
+        bh = w / a.nqt;
+    }
+}
+
 // Kernel modes: one workgroup per (query tile, split, b*h) in all three.
 enum Mode : int {
     kFinal = 0,    // single split, writes O
@@ -135,6 +163,9 @@ hipError_t launch_combine(Elem t, Elem pt, int d, const CombineArgs& a, hipStrea
 hipError_t launch_fwd_strided(Elem t, Elem pt, int d, Mode mode, const FwdArgs& a, hipStream_t s);
 // the causal forward (fa_fwd_causal.hip): final mode, contiguous, Lq = Lk, one split, bf16 / fp16
 hipError_t launch_fwd_causal(Elem t, int d, const FwdArgs& a, hipStream_t s);
+// the GQA forward (fa_fwd_gqa.hip): final mode, contiguous, one split, bf16 / fp16, a.kv_group > 1;
+// causal or not, on the kernel family launch_fwd / launch_fwd_causal pick for the same B*H, L, d
+hipError_t launch_fwd_gqa(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
 int fwd_lds_bytes(int d);
 // compute units of the device that owns `s` (the current device for the null stream;
 // fa_capi.cpp; 256 without a device)

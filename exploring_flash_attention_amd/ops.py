@@ -149,7 +149,9 @@ def _check_tensor(name, t, dtype=None, device=None, ndim=4, strided=False):
         raise ValueError(f"{name} is on {t.device}, expected {device}")
 
 
-def _check_qkv(q, k, v, same_len=True, strided=False):
+def _check_qkv(q, k, v, same_len=True, strided=False, gqa=False):
+    """The common q / k / v checks.  gqa: k and v may hold H_kv heads with H % H_kv == 0
+    (attention_v1 only); returns the group size G = H / H_kv (1 everywhere else)."""
     _check_tensor("q", q, strided=strided)
     if q.dtype not in _DTYPES:
         raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16, float16 or float64)")
@@ -157,10 +159,19 @@ def _check_qkv(q, k, v, same_len=True, strided=False):
     _check_tensor("v", v, q.dtype, q.device, strided=strided)
     if k.shape != v.shape:
         raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} must have the same shape")
-    if q.shape[0] != k.shape[0] or q.shape[1] != k.shape[1] or q.shape[3] != k.shape[3]:
+    if q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
         raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on B, H or d")
-    if same_len and q.shape != k.shape:
+    H, Hkv = q.shape[1], k.shape[1]
+    if H != Hkv:
+        if not gqa:
+            raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on B, H or d "
+                             "(grouped-query attention, H_kv < H, is served by attention_v1 only)")
+        if Hkv <= 0 or H % Hkv:
+            raise ValueError(f"grouped-query attention: H={H} query heads are not a multiple of "
+                             f"H_kv={Hkv} K/V heads")
+    if same_len and (q.shape[0], q.shape[2], q.shape[3]) != (k.shape[0], k.shape[2], k.shape[3]):
         raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} must have the same shape")
+    return H // Hkv if H != Hkv else 1
 
 
 def _out(out, q, shape=None, dtype=None, strided=False):
@@ -196,6 +207,28 @@ def _attention_v1_causal(q, k, v, o):
     return _unpad_into(op, o, d)
 
 
+def _attention_v1_gqa(q, k, v, o, causal):
+    """attention_v1 with H_kv < H after the common checks: fa_fwd_v1_gqa on contiguous tensors
+    of a kernel head dim, zero-padded or copied to that form otherwise."""
+    B, H, L, d = q.shape
+    Hkv = k.shape[1]
+    if q.dtype == torch.float64:
+        raise NotImplementedError("grouped-query attention (GQA): float64 tensors are not supported (the fp64 "
+                                  "kernels read one K/V head per query head; use bfloat16 or float16)")
+    if d > 256:
+        raise NotImplementedError(f"grouped-query attention (GQA): head dim d={d} is not supported (1 <= d <= "
+                                  "256; the d-tiled kernels for d = 384 / 512 have no GQA form)")
+    D = kernel_head_dim(d)
+    if q.numel() == 0:
+        return o
+    # (no strided GQA kernel: views are copied, as the causal path does)
+    qp, kp, vp = (_pad_d(t.contiguous(), D) for t in (q, k, v))
+    op = o if D == d and o.is_contiguous() else torch.empty((B, H, L, D), dtype=q.dtype, device=q.device)
+    _launched(lib().fa_fwd_v1_gqa(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(op), B, H, Hkv, L, D, 1.0 / d ** 0.5,
+                                  _lib.FA_FWD_CAUSAL if causal else 0, _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
+
+
 def attention_v1(q, k, v, out=None, causal=False):
     """FA-v1 fused forward: O = softmax(q k^T / sqrt(d)) v.  Any 1 <= d <= 256 (head dims
     without a kernel are zero-padded to the next one, see kernel_head_dim).  q, k, v and out
@@ -204,8 +237,14 @@ def attention_v1(q, k, v, out=None, causal=False):
 
     ``causal=True``: row i attends to keys 0..i only (fa_fwd_v1_causal; bfloat16 / float16,
     d <= 256 -- float64 and wider head dims raise NotImplementedError; strided views are
-    copied to contiguous tensors first)."""
-    _check_qkv(q, k, v, strided=True)
+    copied to contiguous tensors first).
+
+    Grouped-query attention (GQA / MQA): k and v may be ``[B, H_kv, L, d]`` with H a multiple of
+    H_kv; query head h reads K/V head h // (H // H_kv), the ``repeat_interleave`` convention,
+    without expanding k and v (fa_fwd_v1_gqa; bfloat16 / float16, d <= 256, causal or not;
+    strided views are copied first).  H_kv == H takes the paths above."""
+    if _check_qkv(q, k, v, strided=True, gqa=True) > 1:
+        return _attention_v1_gqa(q, k, v, _out(out, q, strided=True), causal)
     o = _out(out, q, strided=True)
     if causal:
         return _attention_v1_causal(q, k, v, o)

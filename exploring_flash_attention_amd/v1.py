@@ -68,8 +68,17 @@ def flash_attention_v1(Q, K, V, O=None, B=None, H=None, L=None, d=None, causal=F
 
     ``causal=True`` (not in the reference): row i attends to keys 0..i, see
     ``ops.attention_v1``.  bf16 / fp16 only: host arrays other than float16 would run the
-    fp64 kernels, which have no causal mode, and raise NotImplementedError."""
+    fp64 kernels, which have no causal mode, and raise NotImplementedError.
+
+    Grouped-query attention: ``[B, H, L, d]`` Q with ``[B, H_kv, L, d]`` K and V (H a multiple of
+    H_kv) passes through to ``ops.attention_v1`` for device tensors and float16 host arrays;
+    float32 / float64 host arrays raise NotImplementedError, as they do for causal."""
     if O is None:
+        if not _host.is_device_tensor(Q) and np.ndim(Q) == 4 and np.ndim(K) == 4 and np.shape(Q)[1] != np.shape(K)[1] \
+                and _host.compute_dtype(*(np.asarray(x) for x in (Q, K, V))) == torch.float64:
+            raise NotImplementedError("grouped-query attention (GQA): float32 / float64 host arrays run the float64 "
+                                      "kernels, which read one K/V head per query head (pass float16 arrays or "
+                                      "bf16 / fp16 device tensors)")
         if not causal:
             return _host.run_qkv(ops.attention_v1, Q, K, V)
         if not _host.is_device_tensor(Q) and _host.compute_dtype(*(np.asarray(x) for x in (Q, K, V))) == torch.float64:

@@ -83,7 +83,8 @@ typedef enum fa_dtype {
  *          fa_fwd_v2 unsplit), fa_fwd_v1_tiled_d_scaled added;
  *   0.4 -- fa_last_kernels and fa_fwd_v2_ex2 (FA_V2_COUNTERS_ZERO) added (no signature changed);
  *          fa_fwd_v1_causal added later under the same number (an addition only: callers built
- *          against 0.4 stay valid; a library without it fails to resolve the symbol).
+ *          against 0.4 stay valid; a library without it fails to resolve the symbol);
+ *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -136,6 +137,24 @@ int fa_fwd_v1_scaled(const void* q, const void* k, const void* v, void* o,
 int fa_fwd_v1_causal(const void* q, const void* k, const void* v, void* o,
                      int64_t B, int64_t H, int64_t L, int64_t d, double softmax_scale,
                      int dtype, void* stream);
+/* Grouped-query attention (GQA; H_kv = 1: MQA): q and o are [B, H, L, d], k and v
+ * [B, H_kv, L, d] with H a multiple of H_kv, all contiguous, and query head h reads K/V head
+ * h / (H / H_kv) -- what fa_fwd_v1_scaled computes on k, v with every head repeated H / H_kv
+ * times in place (repeat_interleave along the head axis), bit for bit, without the copy.
+ * flags: 0, or FA_FWD_CAUSAL for the mask of fa_fwd_v1_causal; any other bit returns
+ * FA_ERR_INVALID_ARG (the message names "flags").  H_kv <= 0, H_kv > H or H % H_kv != 0 return
+ * FA_ERR_INVALID_ARG (the message names "H_kv").  FA_DTYPE_BF16 or FA_DTYPE_FP16, d in
+ * {32, 64, 128, 256}; d = 384 / 512 and FA_DTYPE_FP64 return FA_ERR_UNSUPPORTED (the message
+ * names "gqa"); pointer, size, scale and alignment checks as fa_fwd_v1_scaled.  H_kv == H
+ * forwards to fa_fwd_v1_scaled / fa_fwd_v1_causal (the same kernels, labels and bits).
+ * Otherwise the call runs the kernel family fa_fwd_v1 / fa_fwd_v1_causal pick for the same
+ * B, H, L, d, its fa_last_kernels label ending in ", gqa": "fa_fwd16_chain_kernel<final, gqa>",
+ * "fa_fwd16_kernel<final, gqa>", "fa_fwd_kernel<final, gqa>", "fa_fwd_kernel<final, causal, gqa>".
+ * The split-KV, d-tiled, strided and multi-GPU entry points take H_kv == H only. */
+#define FA_FWD_CAUSAL 1u
+int fa_fwd_v1_gqa(const void* q, const void* k, const void* v, void* o,
+                  int64_t B, int64_t H, int64_t H_kv, int64_t L, int64_t d,
+                  double softmax_scale, unsigned flags, int dtype, void* stream);
 /* fa_fwd_v1_scaled on strided tensors.  q_strides, kv_strides (shared by k and v) and
  * o_strides each point to three element strides {batch, head, row} of a [B, H, L, d] view
  * whose d is contiguous -- e.g. a [B, L, H, d] tensor is {L*H*d, d, H*d} -- or are NULL for
