@@ -14,6 +14,7 @@
 
 #include "../../include/fa_mi355x.h"
 #include "fa_internal.hpp"
+#include "fa_decode.hpp"
 
 namespace fa {
 // Compute units of the device that owns `s` (the current device for the null stream), queried
@@ -727,6 +728,133 @@ int fa_combine(const void* o_part, const void* lse, void* o, int64_t num_splits,
     if (hipError_t he = e == fa::Elem::F64 ? fa::launch_combine64((int)d, c, (hipStream_t)stream)
                                            : fa::launch_combine(e, pe, (int)d, c, (hipStream_t)stream))
         return hip_fail(he, "fa_combine launch");
+    return ok();
+}
+
+}  // extern "C"
+
+/* ---- KV-cache decode (fa_decode.hip) ---- */
+
+namespace {
+
+struct DecodePlan {
+    int splits, kps;
+    size_t o_bytes, bytes;  // partial O (256-byte aligned), everything
+};
+
+// shape checks shared by the planner and the launcher; *e receives the element type
+int decode_check(int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d, int num_splits,
+                 int dtype, fa::Elem* e) {
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || d <= 0)
+        return fail(FA_ERR_INVALID_ARG, "decode: all dimensions must be positive (B=%lld H=%lld Lq=%lld Lk=%lld d=%lld)",
+                    (long long)B, (long long)H, (long long)Lq, (long long)Lk, (long long)d);
+    if (H_kv <= 0 || H_kv > H || H % H_kv != 0)
+        return fail(FA_ERR_INVALID_ARG, "decode: H_kv=%lld must be positive and divide H=%lld", (long long)H_kv,
+                    (long long)H);
+    if (num_splits < 0) return fail(FA_ERR_INVALID_ARG, "decode: num_splits=%d must be >= 0 (0 = auto)", num_splits);
+    if (d != 64 && d != 128)
+        return fail(FA_ERR_UNSUPPORTED, "decode: head dim d=%lld has no decode kernel (64 and 128 only)", (long long)d);
+    if ((H / H_kv) * Lq > fa::kDecMaxRows)
+        return fail(FA_ERR_UNSUPPORTED,
+                    "decode: G * Lq = %lld * %lld packed query rows exceed %d (long queries: fa_fwd_v1_gqa)",
+                    (long long)(H / H_kv), (long long)Lq, fa::kDecMaxRows);
+    if (int st = check_dtype(dtype, e)) return st;
+    if (*e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "decode: FA_DTYPE_FP64 has no decode kernel (bf16 / fp16 only)");
+    if (Lk > (int64_t)1 << 30) return fail(FA_ERR_UNSUPPORTED, "decode: Lk=%lld exceeds 2^30", (long long)Lk);
+    if (B * H_kv > (int64_t)1 << 24 || B * H > (int64_t)1 << 30)
+        return fail(FA_ERR_UNSUPPORTED, "decode: B * H_kv = %lld exceeds 2^24", (long long)(B * H_kv));
+    return FA_OK;
+}
+
+// Key splits: as few as still give every CU a workgroup at the kernel's occupancy, none beyond
+// one when the (b, hkv) items alone do, and never so many that a split keeps fewer keys than
+// the workgroup's waves take tiles; a forced count is clamped to the key tiles.  The split is
+// then rounded to whole tiles and the count recomputed, so that no split is structurally empty.
+DecodePlan decode_plan(int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d, int num_splits,
+                       int cus) {
+    const int64_t items = B * H_kv, tiles = (Lk + fa::kDecBK - 1) / fa::kDecBK;
+    int64_t want;
+    if (num_splits > 0) {
+        want = num_splits < tiles ? num_splits : tiles;
+    } else {
+        const int64_t slots = (int64_t)cus * fa::decode_wg_per_cu((int)d);
+        want = items >= slots ? 1 : (slots + items - 1) / items;
+        const int64_t cap = (Lk + fa::kDecMinSplitKeys - 1) / fa::kDecMinSplitKeys;
+        if (want > cap) want = cap;
+    }
+    if (want < 1) want = 1;
+    const int64_t per = (Lk + want - 1) / want;
+    DecodePlan p{};
+    p.kps = (int)((per + fa::kDecBK - 1) / fa::kDecBK * fa::kDecBK);
+    p.splits = (int)((Lk + p.kps - 1) / p.kps);
+    if (p.splits > 1) {
+        const size_t R = (size_t)((H / H_kv) * Lq), n = (size_t)items * p.splits;
+        p.o_bytes = align256(n * R * (size_t)d * 4);
+        p.bytes = p.o_bytes + align256(n * R * 4);
+    }
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fa_fwd_decode_plan(int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d, int num_splits,
+                       int cus, int dtype, int* splits, int* keys_per_split, size_t* workspace_bytes) {
+    fa::Elem e;
+    if (int st = decode_check(B, H, H_kv, Lq, Lk, d, num_splits, dtype, &e)) return st;
+    if (cus < 0) return fail(FA_ERR_INVALID_ARG, "decode: cus=%d must be >= 0 (0 = the current device)", cus);
+    const DecodePlan p = decode_plan(B, H, H_kv, Lq, Lk, d, num_splits, cus > 0 ? cus : device_cus());
+    if (splits) *splits = p.splits;
+    if (keys_per_split) *keys_per_split = p.kps;
+    if (workspace_bytes) *workspace_bytes = p.bytes;
+    return ok();
+}
+
+int fa_fwd_decode(const void* q, const void* k, const void* v, void* o, const int32_t* seqlens_k, int64_t B,
+                  int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d, const int64_t* kv_strides,
+                  double softmax_scale, unsigned flags, int num_splits, void* workspace, size_t workspace_bytes,
+                  int dtype, void* stream) {
+    fa::Elem e;
+    if (flags & ~FA_FWD_CAUSAL)
+        return fail(FA_ERR_INVALID_ARG, "decode: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
+    if (int st = decode_check(B, H, H_kv, Lq, Lk, d, num_splits, dtype, &e)) return st;
+    if (int st = check_ptrs(q, k, v, o)) return st;
+    if ((uintptr_t)seqlens_k & 3) return fail(FA_ERR_INVALID_ARG, "decode: seqlens_k must be 4-byte aligned");
+    if (!(softmax_scale > 0.0) || !std::isfinite(softmax_scale))
+        return fail(FA_ERR_INVALID_ARG, "softmax_scale must be positive and finite (got %g)", softmax_scale);
+    fa::DecodeArgs a{};
+    const int64_t contig[3] = {H_kv * Lk * d, Lk * d, d};
+    const int64_t* st3 = kv_strides ? kv_strides : contig;
+    for (int i = 0; i < 3; ++i) {
+        if (st3[i] <= 0 || st3[i] % 8)
+            return fail(FA_ERR_INVALID_ARG, "k/v stride[%d]=%lld must be positive and a multiple of 8 elements", i,
+                        (long long)st3[i]);
+        a.kv_stride[i] = st3[i];
+    }
+    if (st3[2] < d)
+        return fail(FA_ERR_INVALID_ARG, "k/v row stride %lld < d=%lld", (long long)st3[2], (long long)d);
+    if (st3[2] > (int64_t)1 << 20)
+        return fail(FA_ERR_UNSUPPORTED, "decode: k/v row stride %lld exceeds 2^20 elements", (long long)st3[2]);
+    const DecodePlan p = decode_plan(B, H, H_kv, Lq, Lk, d, num_splits, device_cus((hipStream_t)stream));
+    if (p.bytes) {
+        if (!workspace || workspace_bytes < p.bytes)
+            return fail(FA_ERR_INVALID_ARG, "decode: workspace of %zu bytes needed (fa_fwd_decode_plan), got %zu%s",
+                        p.bytes, workspace_bytes, workspace ? "" : " (null)");
+        if ((uintptr_t)workspace & 15) return fail(FA_ERR_INVALID_ARG, "decode: workspace must be 16-byte aligned");
+    }
+    a.q = q; a.k = k; a.v = v; a.o = o; a.seqlens = seqlens_k;
+    a.B = (int)B; a.H = (int)H; a.Hkv = (int)H_kv; a.G = (int)(H / H_kv); a.Lq = (int)Lq; a.Lk = (int)Lk;
+    a.R = a.G * a.Lq;
+    a.nsplit = p.splits;
+    a.kps = p.kps;
+    a.causal = (flags & FA_FWD_CAUSAL) != 0;
+    a.scale_log2 = (float)(1.4426950408889634 * softmax_scale);
+    a.o_part = (float*)workspace;
+    a.lse = p.bytes ? (float*)((char*)workspace + p.o_bytes) : nullptr;
+    kernels_begin();
+    if (hipError_t he = fa::launch_decode(e, (int)d, a, (hipStream_t)stream)) return hip_fail(he, "fa_fwd_decode launch");
     return ok();
 }
 

@@ -13,6 +13,8 @@ Reference launchers these replace (tyler-utah/exploring_flash_attention):
   attention_v2       flash_attention_v2/CUDA/flash_attention_v2.h:438 (opt :559)
   attention_partial  partial_attention_kernel, flash_attention_v2/CUDA/flash_attention_v2.h:243
   combine            reduction_kernel,         flash_attention_v2/CUDA/flash_attention_v2.h:356
+attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV) has
+no counterpart in the reference.
 """
 import contextlib
 import ctypes
@@ -480,6 +482,105 @@ def combine(o_part, lse, B, H, dtype, out=None):
     _launched(lib().fa_combine(_ptr(o_part), _ptr(lse), _ptr(o), S, B, H, L, d, _DTYPES[dtype],
                            _PDTYPES[pd], _stream(o_part)))
     return o
+
+
+DECODE_HEAD_DIMS = (64, 128)  # head dims with a decode kernel
+DECODE_MAX_ROWS = 64          # packed query rows (H / H_kv) * Lq of one K/V head at most
+
+
+def decode_plan(B, H, H_kv, Lq, Lk, d, num_splits=None, dtype=torch.bfloat16, cus=None):
+    """``(splits, keys_per_split, workspace_bytes)`` attention_decode uses for this problem
+    (fa_fwd_decode_plan): ``num_splits=None`` lets the library pick as few key splits as still
+    give every compute unit a workgroup (1 when B * H_kv alone does).  ``cus``: the compute
+    units to plan for, None = the current device's (needs no device when given).  d is the
+    kernel's head dim (64 or 128)."""
+    splits, kps, nbytes = _lib._I(), _lib._I(), ctypes.c_size_t()
+    check(lib().fa_fwd_decode_plan(int(B), int(H), int(H_kv), int(Lq), int(Lk), int(d),
+                                   0 if num_splits is None else int(num_splits), 0 if cus is None else int(cus),
+                                   _DTYPES[dtype], ctypes.byref(splits), ctypes.byref(kps), ctypes.byref(nbytes)))
+    return splits.value, kps.value, nbytes.value
+
+
+def attention_decode(q, k, v, seqlens_k=None, causal=True, num_splits=None, out=None, workspace=None):
+    """KV-cache decode attention: q ``[B, H, Lq, d]`` (Lq small) against k, v ``[B, H_kv, Lk, d]``,
+    bfloat16 or float16, H a multiple of H_kv (query head h reads K/V head h // (H // H_kv)) and
+    (H // H_kv) * Lq <= 64 -- the query rows of a K/V head are packed into one tile, the keys are
+    split over the chip and combined in the same call (fa_fwd_decode).
+
+    ``seqlens_k``: int32 ``[B]`` tensor on q's device, the valid keys of each sequence (clamped
+    to [0, Lk] on the device; no host read); rows of k / v from there on are never used, whatever
+    they hold.  ``causal`` (default): the mask aligned bottom-right, row position i sees keys
+    j <= len_b - Lq + i -- a no-op at Lq = 1; a row without a visible key is zero.
+    ``num_splits``: key splits (None: from the device's occupancy, see decode_plan).
+
+    k and v are read in place through their strides when d is contiguous, k and v share strides
+    that are multiples of 8 elements and the base is 16-byte aligned -- e.g. a ``[B, Lmax, H_kv,
+    d]`` cache as ``cache.transpose(1, 2)[:, :, :Lk]``; other views are copied.  q and out are
+    small and copied when not contiguous.  ``workspace``: a uint8 device tensor of at least
+    decode_plan(...)[2] bytes; with it (and ``out``) the call allocates nothing.
+
+    d = 64 and 128 run natively; any other d <= 128 is zero-padded to the next of them with the
+    scale 1/sqrt(d) kept -- that COPIES the cache on every call: a convenience, not a fast path.
+    d > 128, float64 and (H // H_kv) * Lq > 64 raise NotImplementedError."""
+    _check_tensor("q", q, strided=True)
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16 or float16)")
+    _check_tensor("k", k, q.dtype, q.device, strided=True)
+    _check_tensor("v", v, q.dtype, q.device, strided=True)
+    if k.shape != v.shape:
+        raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} must have the same shape")
+    if q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
+        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on B or d")
+    B, H, Lq, d = q.shape
+    Hkv, Lk = k.shape[1], k.shape[2]
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"attention_decode: H={H} query heads are not a multiple of H_kv={Hkv} K/V heads")
+    if q.dtype == torch.float64:
+        raise NotImplementedError("attention_decode: float64 tensors are not supported (use bfloat16 or float16)")
+    if d > DECODE_HEAD_DIMS[-1]:
+        raise NotImplementedError(f"attention_decode: head dim d={d} is not supported (1 <= d <= 128)")
+    if (H // Hkv) * Lq > DECODE_MAX_ROWS:
+        raise NotImplementedError(f"attention_decode: (H / H_kv) * Lq = {H // Hkv} * {Lq} packed query rows exceed "
+                                  f"{DECODE_MAX_ROWS}; long queries are served by attention_v1")
+    if seqlens_k is not None:
+        _check_tensor("seqlens_k", seqlens_k, torch.int32, q.device, ndim=1)
+        if seqlens_k.dtype != torch.int32 or tuple(seqlens_k.shape) != (B,):
+            raise ValueError(f"seqlens_k must be an int32 tensor of shape ({B},), got {seqlens_k.dtype} "
+                             f"{tuple(seqlens_k.shape)}")
+    o = _out(out, q, strided=True)
+    if q.numel() == 0:
+        return o
+    if Lk == 0:  # no keys: every row is empty
+        return o.zero_()
+    D = next(x for x in DECODE_HEAD_DIMS if x >= d)
+    kst = None
+    if D != d:
+        k, v = _pad_d(k, D), _pad_d(v, D)
+    elif not (k.is_contiguous() and v.is_contiguous()):
+        st = k.stride()
+        if (k.stride() == v.stride() and st[3] == 1 and all(x > 0 and x % 8 == 0 for x in st[:3]) and st[2] >= d
+                and st[2] <= 1 << 20 and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0):
+            kst = (ctypes.c_int64 * 3)(*st[:3])
+        else:
+            k, v = k.contiguous(), v.contiguous()
+    qp = _pad_d(q.contiguous(), D)
+    op = o if D == d and o.is_contiguous() else torch.empty((B, H, Lq, D), dtype=q.dtype, device=q.device)
+    ns = 0 if num_splits is None else int(num_splits)
+    if ns < 0:
+        raise ValueError(f"num_splits={ns} must be positive (or None)")
+    nbytes = decode_plan(B, H, Hkv, Lq, Lk, D, ns, q.dtype)[2]
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    else:
+        _check_tensor("workspace", workspace, torch.uint8, q.device, ndim=1)
+        if workspace.numel() * workspace.element_size() < nbytes:
+            raise ValueError(f"workspace too small: {nbytes} bytes needed")
+    _launched(lib().fa_fwd_decode(_ptr(qp), _ptr(k), _ptr(v), _ptr(op), None if seqlens_k is None else _ptr(seqlens_k),
+                                  B, H, Hkv, Lq, Lk, D, kst, 1.0 / d ** 0.5, _lib.FA_FWD_CAUSAL if causal else 0, ns,
+                                  None if workspace is None else _ptr(workspace),
+                                  0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                  _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
 
 
 def kernel_geometry(d, dtype=torch.bfloat16):

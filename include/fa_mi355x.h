@@ -84,7 +84,8 @@ typedef enum fa_dtype {
  *   0.4 -- fa_last_kernels and fa_fwd_v2_ex2 (FA_V2_COUNTERS_ZERO) added (no signature changed);
  *          fa_fwd_v1_causal added later under the same number (an addition only: callers built
  *          against 0.4 stay valid; a library without it fails to resolve the symbol);
- *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way.
+ *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way; then fa_fwd_decode_plan and
+ *          fa_fwd_decode (KV-cache decode), again additions only.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -323,6 +324,52 @@ int fa_fwd_partial_ex(const void* q, const void* k, const void* v,
 int fa_combine(const void* o_part, const void* lse, void* o,
                int64_t num_splits, int64_t B, int64_t H, int64_t L, int64_t d,
                int dtype, int partial_dtype, void* stream);
+
+/* ---- KV-cache decode: few query rows per sequence against a long, possibly padded cache ----
+ *
+ * q and o are [B, H, Lq, d] contiguous, k and v [B, H_kv, Lk, d] with H a multiple of H_kv
+ * (G = H / H_kv; query head h reads K/V head h / G), FA_DTYPE_BF16 or FA_DTYPE_FP16, d = 64 or
+ * 128, and G * Lq <= 64: the G * Lq query rows of a K/V head are one work item's query tile, so
+ * each K/V row is read once per group.  The keys are cut into `splits` ranges of
+ * `keys_per_split` keys that run as separate workgroups (grid B * H_kv * splits) and are
+ * combined by a second small kernel of the same call.
+ *
+ * fa_fwd_decode_plan: the split the launcher will use.  num_splits 0 = auto: as few splits as
+ * still give every compute unit a workgroup, 1 when B * H_kv alone does, never fewer than 256
+ * keys per split; a positive num_splits is clamped to ceil(Lk / 64).  keys_per_split is a
+ * multiple of 64, splits * keys_per_split >= Lk > (splits - 1) * keys_per_split.  cus: the
+ * compute units to plan for, 0 = the current device's (fa_fwd_decode plans for the device that
+ * owns `stream`).  *workspace_bytes: the fp32 partials [B*H_kv*splits][G*Lq][d] and their base-2
+ * lse [B*H_kv*splits][G*Lq], each rounded up to 256 bytes; 0 for one split.  Any output pointer
+ * may be NULL.  No device is needed when cus > 0.
+ *
+ * fa_fwd_decode: O[b, h, i] = softmax(softmax_scale * Q[b, h, i] K[b, h/G, 0..n)^T) V[b, h/G, 0..n).
+ *   seqlens_k: int32 [B] in DEVICE memory or NULL; the kernel reads len_b = seqlens_k[b] clamped
+ *     to [0, Lk] itself (no host read, no synchronisation); NULL: len_b = Lk.  Keys >= len_b do
+ *     not exist: whatever the cache holds there (NaN included) is never read into the result.
+ *   flags: 0 or FA_FWD_CAUSAL, the mask aligned bottom-right: row position i sees keys
+ *     j <= len_b - Lq + i (a no-op at Lq = 1).  A row without a visible key (len_b = 0, or
+ *     len_b - Lq + i < 0) is zero.  A key a causal row may not see contributes nothing to that
+ *     row, whatever K and V hold there.
+ *   kv_strides: {batch, head, row} element strides shared by k and v (d contiguous), NULL for
+ *     contiguous -- e.g. a [B, Lmax, H_kv, d] cache is {Lmax*H_kv*d, d, H_kv*d}; positive
+ *     multiples of 8, row stride >= d and <= 2^20.  The cache is read in place.
+ *   workspace: at least *workspace_bytes of fa_fwd_decode_plan (same arguments, cus = 0 with the
+ *     stream's device current), 16-byte aligned; contents need not be initialised and nothing
+ *     has to be reset between calls; may be NULL when the plan needs none.
+ * FA_ERR_INVALID_ARG: null or misaligned pointers, non-positive sizes, a bad H_kv, a bad scale,
+ * unknown flag bits, negative num_splits, a workspace that is missing or too small.
+ * FA_ERR_UNSUPPORTED: d not 64 / 128, G * Lq > 64, FA_DTYPE_FP64.  For a fixed plan repeated
+ * calls are bitwise equal (the splits are summed in split order).
+ * fa_last_kernels: "fa_decode_kernel<16|32|64 rows> [grid B*H_kv*splits]", then
+ * " + fa_decode_combine_kernel [grid ...]" when splits > 1. */
+int fa_fwd_decode_plan(int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
+                       int num_splits, int cus, int dtype,
+                       int* splits, int* keys_per_split, size_t* workspace_bytes);
+int fa_fwd_decode(const void* q, const void* k, const void* v, void* o, const int32_t* seqlens_k,
+                  int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
+                  const int64_t* kv_strides, double softmax_scale, unsigned flags, int num_splits,
+                  void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
