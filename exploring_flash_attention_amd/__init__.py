@@ -10,21 +10,23 @@ hand-written CDNA4 HIP kernels behind a C ABI (include/fa_mi355x.h,
 bf16 / fp16, d <= 256) and grouped-query K / V (``[B, H_kv, L, d]`` with H a multiple of H_kv;
 same types and head dims); ``attention_decode`` is the KV-cache decode forward (few query rows
 against a long, padded cache: ``[B, H, Lq, d]`` x ``[B, H_kv, Lk, d]``, per-sequence key
-lengths, bottom-right causal mask, GQA-packed and split over keys; bf16 / fp16, d <= 128);
+lengths, bottom-right causal mask, GQA-packed and split over keys; bf16 / fp16, d <= 128) and
+``attention_decode_paged`` the same forward on a paged pool ``[num_blocks, page_size, H_kv, d]``
+read in place through an int32 block table (page_size a multiple of 64, d = 64 / 128);
 every other surface is non-causal with H_kv = H and Lq = Lk, as the reference is.
 
 There is no CPU fallback: every entry point raises if the HIP library is not built or no
 ROCm device is present.
 """
 from . import ops  # noqa: F401
-from .ops import (attention_decode, attention_partial, attention_tiled_d, attention_v1,  # noqa: F401
-                  attention_v2, combine, kernel_geometry)
+from .ops import (attention_decode, attention_decode_paged, attention_partial, attention_tiled_d,  # noqa: F401
+                  attention_v1, attention_v2, combine, kernel_geometry)
 from .tiled_d import flash_attention_v1_tiled_d  # noqa: F401
 from .v1 import flash_attention_v1  # noqa: F401
 from .v2 import flash_attention_v2  # noqa: F401
 
 __all__ = ["ops", "attention_v1", "attention_tiled_d", "attention_v2", "attention_partial",
-           "attention_decode",
+           "attention_decode", "attention_decode_paged",
            "combine", "kernel_geometry", "flash_attention_v1", "flash_attention_v1_tiled_d",
            "flash_attention_v2"]
 __version__ = "0.1.0"

@@ -67,6 +67,8 @@ SIGNATURES = {
                                 ctypes.POINTER(ctypes.c_size_t)]),
     "fa_fwd_decode": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, ctypes.c_double,
                            ctypes.c_uint, _I, _P, ctypes.c_size_t, _I, _P]),
+    "fa_fwd_decode_paged": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
+                                 ctypes.c_double, ctypes.c_uint, _I, _P, ctypes.c_size_t, _I, _P]),
 }
 
 _lock = threading.Lock()

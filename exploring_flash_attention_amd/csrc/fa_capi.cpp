@@ -796,6 +796,53 @@ DecodePlan decode_plan(int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t L
     return p;
 }
 
+// What fa_fwd_decode and fa_fwd_decode_paged share: every check of the common arguments, the
+// plan, the workspace, the DecodeArgs and the launch.  st3: the three K/V element strides
+// ({batch, head, row}, paged {block, head, row}), `strides` their name in messages; `a` arrives
+// zeroed but for the paged fields, which the paged entry has checked and set.
+int decode_launch(const char* entry, const char* strides, const void* q, const void* k, const void* v, void* o,
+                  const int32_t* seqlens_k, int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
+                  const int64_t* st3, double softmax_scale, unsigned flags, int num_splits, void* workspace,
+                  size_t workspace_bytes, int dtype, void* stream, fa::DecodeArgs& a) {
+    fa::Elem e;
+    if (flags & ~FA_FWD_CAUSAL)
+        return fail(FA_ERR_INVALID_ARG, "decode: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
+    if (int st = decode_check(B, H, H_kv, Lq, Lk, d, num_splits, dtype, &e)) return st;
+    if (int st = check_ptrs(q, k, v, o)) return st;
+    if ((uintptr_t)seqlens_k & 3) return fail(FA_ERR_INVALID_ARG, "decode: seqlens_k must be 4-byte aligned");
+    if (!(softmax_scale > 0.0) || !std::isfinite(softmax_scale))
+        return fail(FA_ERR_INVALID_ARG, "softmax_scale must be positive and finite (got %g)", softmax_scale);
+    for (int i = 0; i < 3; ++i) {
+        if (st3[i] <= 0 || st3[i] % 8)
+            return fail(FA_ERR_INVALID_ARG, "%s stride[%d]=%lld must be positive and a multiple of 8 elements", strides,
+                        i, (long long)st3[i]);
+        a.kv_stride[i] = st3[i];
+    }
+    if (st3[2] < d)
+        return fail(FA_ERR_INVALID_ARG, "%s row stride %lld < d=%lld", strides, (long long)st3[2], (long long)d);
+    if (st3[2] > (int64_t)1 << 20)
+        return fail(FA_ERR_UNSUPPORTED, "decode: %s row stride %lld exceeds 2^20 elements", strides, (long long)st3[2]);
+    const DecodePlan p = decode_plan(B, H, H_kv, Lq, Lk, d, num_splits, device_cus((hipStream_t)stream));
+    if (p.bytes) {
+        if (!workspace || workspace_bytes < p.bytes)
+            return fail(FA_ERR_INVALID_ARG, "decode: workspace of %zu bytes needed (fa_fwd_decode_plan), got %zu%s",
+                        p.bytes, workspace_bytes, workspace ? "" : " (null)");
+        if ((uintptr_t)workspace & 15) return fail(FA_ERR_INVALID_ARG, "decode: workspace must be 16-byte aligned");
+    }
+    a.q = q; a.k = k; a.v = v; a.o = o; a.seqlens = seqlens_k;
+    a.B = (int)B; a.H = (int)H; a.Hkv = (int)H_kv; a.G = (int)(H / H_kv); a.Lq = (int)Lq; a.Lk = (int)Lk;
+    a.R = a.G * a.Lq;
+    a.nsplit = p.splits;
+    a.kps = p.kps;
+    a.causal = (flags & FA_FWD_CAUSAL) != 0;
+    a.scale_log2 = (float)(1.4426950408889634 * softmax_scale);
+    a.o_part = (float*)workspace;
+    a.lse = p.bytes ? (float*)((char*)workspace + p.o_bytes) : nullptr;
+    kernels_begin();
+    if (hipError_t he = fa::launch_decode(e, (int)d, a, (hipStream_t)stream)) return hip_fail(he, entry);
+    return ok();
+}
+
 }  // namespace
 
 extern "C" {
@@ -816,46 +863,42 @@ int fa_fwd_decode(const void* q, const void* k, const void* v, void* o, const in
                   int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d, const int64_t* kv_strides,
                   double softmax_scale, unsigned flags, int num_splits, void* workspace, size_t workspace_bytes,
                   int dtype, void* stream) {
-    fa::Elem e;
-    if (flags & ~FA_FWD_CAUSAL)
-        return fail(FA_ERR_INVALID_ARG, "decode: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
-    if (int st = decode_check(B, H, H_kv, Lq, Lk, d, num_splits, dtype, &e)) return st;
-    if (int st = check_ptrs(q, k, v, o)) return st;
-    if ((uintptr_t)seqlens_k & 3) return fail(FA_ERR_INVALID_ARG, "decode: seqlens_k must be 4-byte aligned");
-    if (!(softmax_scale > 0.0) || !std::isfinite(softmax_scale))
-        return fail(FA_ERR_INVALID_ARG, "softmax_scale must be positive and finite (got %g)", softmax_scale);
     fa::DecodeArgs a{};
     const int64_t contig[3] = {H_kv * Lk * d, Lk * d, d};
-    const int64_t* st3 = kv_strides ? kv_strides : contig;
-    for (int i = 0; i < 3; ++i) {
-        if (st3[i] <= 0 || st3[i] % 8)
-            return fail(FA_ERR_INVALID_ARG, "k/v stride[%d]=%lld must be positive and a multiple of 8 elements", i,
-                        (long long)st3[i]);
-        a.kv_stride[i] = st3[i];
-    }
-    if (st3[2] < d)
-        return fail(FA_ERR_INVALID_ARG, "k/v row stride %lld < d=%lld", (long long)st3[2], (long long)d);
-    if (st3[2] > (int64_t)1 << 20)
-        return fail(FA_ERR_UNSUPPORTED, "decode: k/v row stride %lld exceeds 2^20 elements", (long long)st3[2]);
-    const DecodePlan p = decode_plan(B, H, H_kv, Lq, Lk, d, num_splits, device_cus((hipStream_t)stream));
-    if (p.bytes) {
-        if (!workspace || workspace_bytes < p.bytes)
-            return fail(FA_ERR_INVALID_ARG, "decode: workspace of %zu bytes needed (fa_fwd_decode_plan), got %zu%s",
-                        p.bytes, workspace_bytes, workspace ? "" : " (null)");
-        if ((uintptr_t)workspace & 15) return fail(FA_ERR_INVALID_ARG, "decode: workspace must be 16-byte aligned");
-    }
-    a.q = q; a.k = k; a.v = v; a.o = o; a.seqlens = seqlens_k;
-    a.B = (int)B; a.H = (int)H; a.Hkv = (int)H_kv; a.G = (int)(H / H_kv); a.Lq = (int)Lq; a.Lk = (int)Lk;
-    a.R = a.G * a.Lq;
-    a.nsplit = p.splits;
-    a.kps = p.kps;
-    a.causal = (flags & FA_FWD_CAUSAL) != 0;
-    a.scale_log2 = (float)(1.4426950408889634 * softmax_scale);
-    a.o_part = (float*)workspace;
-    a.lse = p.bytes ? (float*)((char*)workspace + p.o_bytes) : nullptr;
-    kernels_begin();
-    if (hipError_t he = fa::launch_decode(e, (int)d, a, (hipStream_t)stream)) return hip_fail(he, "fa_fwd_decode launch");
-    return ok();
+    return decode_launch("fa_fwd_decode launch", "k/v", q, k, v, o, seqlens_k, B, H, H_kv, Lq, Lk, d,
+                         kv_strides ? kv_strides : contig, softmax_scale, flags, num_splits, workspace,
+                         workspace_bytes, dtype, stream, a);
+}
+
+int fa_fwd_decode_paged(const void* q, const void* k_cache, const void* v_cache, void* o, const int32_t* block_table,
+                        const int32_t* seqlens_k, int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
+                        int64_t num_blocks, int64_t page_size, int64_t table_stride, const int64_t* cache_strides,
+                        double softmax_scale, unsigned flags, int num_splits, void* workspace, size_t workspace_bytes,
+                        int dtype, void* stream) {
+    if (!block_table || ((uintptr_t)block_table & 3))
+        return fail(FA_ERR_INVALID_ARG, "decode: block_table must be non-null and 4-byte aligned");
+    if (num_blocks <= 0 || num_blocks > INT32_MAX)
+        return fail(FA_ERR_INVALID_ARG, "decode: num_blocks=%lld must be positive (and fit the int32 table)",
+                    (long long)num_blocks);
+    if (page_size <= 0) return fail(FA_ERR_INVALID_ARG, "decode: page_size=%lld must be positive", (long long)page_size);
+    // a 64-key tile must lie inside one page: its K and V descriptors cover one block
+    if (page_size % fa::kDecBK)
+        return fail(FA_ERR_UNSUPPORTED, "decode: page_size=%lld is not a multiple of %d keys (pages of 16 / 32 keys "
+                    "have no kernel)", (long long)page_size, fa::kDecBK);
+    if (page_size > (int64_t)1 << 30)
+        return fail(FA_ERR_UNSUPPORTED, "decode: page_size=%lld exceeds 2^30", (long long)page_size);
+    if (table_stride < (Lk + page_size - 1) / page_size)
+        return fail(FA_ERR_INVALID_ARG, "decode: table_stride=%lld is below ceil(Lk / page_size) = %lld pages",
+                    (long long)table_stride, (long long)((Lk + page_size - 1) / page_size));
+    fa::DecodeArgs a{};
+    a.block_table = block_table;
+    a.table_stride = table_stride;
+    a.page_size = (int)page_size;
+    a.num_blocks = (int)num_blocks;
+    const int64_t contig[3] = {page_size * H_kv * d, d, H_kv * d};  // [num_blocks, page_size, H_kv, d]
+    return decode_launch("fa_fwd_decode_paged launch", "cache_strides", q, k_cache, v_cache, o, seqlens_k, B, H, H_kv, Lq,
+                         Lk, d, cache_strides ? cache_strides : contig, softmax_scale, flags, num_splits, workspace,
+                         workspace_bytes, dtype, stream, a);
 }
 
 }  // extern "C"

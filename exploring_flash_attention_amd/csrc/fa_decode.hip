@@ -27,6 +27,13 @@
 // One split: the workgroup writes O.  Several: it writes a normalised fp32 partial and a base-2
 // lse (-inf for a split or row without keys) and fa_decode_combine_kernel, enqueued behind it,
 // sums the splits in split order -- no counters, no workgroup waits on another.
+//
+// PAGED instantiations (fa_fwd_decode_paged): K / V are pools of blocks of page_size keys and key
+// j of batch b is row j % page_size of block block_table[b][j / page_size].  Splits and pages are
+// whole tiles, so a tile lies inside one page: its two descriptors keep their form and take their
+// base from one scalar table read per tile, the entry clamped to [0, num_blocks - 1] first.  The
+// tiles, their order and the arithmetic are those of the contiguous kernels (bitwise the same
+// result on the gathered cache), whose code is not touched: everything paged is if constexpr.
 #include <type_traits>
 
 #include "fa_decode.hpp"
@@ -50,7 +57,7 @@ __device__ __forceinline__ float weight2(float a, float b) {
 
 }  // namespace
 
-template <typename T, int D, int NQB>
+template <typename T, int D, int NQB, bool PAGED>
 __global__ __launch_bounds__(kDecThreads, 1) void fa_decode_kernel(DecodeArgs a) {
     using M = Mma<T>;
     using v8 = typename M::v8;
@@ -118,9 +125,27 @@ __global__ __launch_bounds__(kDecThreads, 1) void fa_decode_kernel(DecodeArgs a)
                 v8, __builtin_amdgcn_raw_buffer_load_b128(qrs, (16 * qb + n16) * ROWB + ks * 64 + g * 16, 0, 0));
 
     const int krb = (int)(a.kv_stride[2] * 2);  // bytes between key rows
-    const int64_t kv_head = (int64_t)b * a.kv_stride[0] + (int64_t)hkv * a.kv_stride[1];
+    // (paged: kv_stride is {block, head, row} and the bases are the head's place in block 0)
+    const int64_t kv_head = (PAGED ? 0 : (int64_t)b * a.kv_stride[0]) + (int64_t)hkv * a.kv_stride[1];
     const char* const kbase = (const char*)((const unsigned short*)a.k + kv_head);
     const char* const vbase = (const char*)((const unsigned short*)a.v + kv_head);
+    // Byte offset of key j's row from kbase / vbase, j wave-uniform.  Paged: one scalar read of
+    // the sequence's table row (constant address space: the table is not written while the kernel
+    // runs), the entry clamped into the pool before it enters an address.  Only pages that hold a
+    // key of this split below len are looked up.
+    typedef __attribute__((address_space(4))) const int* table_ptr;
+    const table_ptr tbl = PAGED ? (table_ptr)(a.block_table + (int64_t)b * a.table_stride) : (table_ptr) nullptr;
+    auto key_off = [&](int j) -> int64_t {
+        if constexpr (PAGED) {
+            const unsigned page = __builtin_amdgcn_readfirstlane((unsigned)j / (unsigned)a.page_size);
+            const int in = j - (int)page * a.page_size;
+            const int e = tbl[page];
+            const int blk = e < 0 ? 0 : e > a.num_blocks - 1 ? a.num_blocks - 1 : e;
+            return ((int64_t)blk * a.kv_stride[0] + (int64_t)in * a.kv_stride[2]) * 2;
+        } else {
+            return (int64_t)j * krb;
+        }
+    };
 
     // K fragment (A operand) of key block kb, k-step ks: row 16*kb + rho(n), bytes 64*ks + 16*g
     const int rho = 8 * ((n16 >> 2) & 1) + 4 * (n16 >> 3) + (n16 & 3);
@@ -166,13 +191,14 @@ __global__ __launch_bounds__(kDecThreads, 1) void fa_decode_kernel(DecodeArgs a)
     const float c = a.scale_log2;
 
     // tile t of the split: its valid rows bound the buffer range, so rows past mf_end read as zero
+    // (paged: kv_begin and the page size are multiples of the tile, so a tile lies inside one page)
     auto tile_rows = [&](int t) {
         const int left = mf_end - (kv_begin + t * kBK);
         return left < kBK ? left : kBK;
     };
     auto load_k = [&](int t, u32x4 (&kf)[NKB][NKS]) {
         const __amdgpu_buffer_rsrc_t rsr =
-            make_rsrc32(kbase + (int64_t)(kv_begin + t * kBK) * krb, (tile_rows(t) - 1) * krb + ROWB);
+            make_rsrc32(kbase + key_off(kv_begin + t * kBK), (tile_rows(t) - 1) * krb + ROWB);
 #pragma unroll
         for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
@@ -181,7 +207,7 @@ __global__ __launch_bounds__(kDecThreads, 1) void fa_decode_kernel(DecodeArgs a)
     };
     auto dma_v = [&](int t, char* slot) {
         const __amdgpu_buffer_rsrc_t rsr =
-            make_rsrc32(vbase + (int64_t)(kv_begin + t * kBK) * krb, (tile_rows(t) - 1) * krb + ROWB);
+            make_rsrc32(vbase + key_off(kv_begin + t * kBK), (tile_rows(t) - 1) * krb + ROWB);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int rg = D == 128 ? p >> 1 : p;  // the piece's group of 8 rows (d = 128: two pieces each)
@@ -292,8 +318,9 @@ __global__ __launch_bounds__(kDecThreads, 1) void fa_decode_kernel(DecodeArgs a)
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) irow[qb] = 16 * qb + n16 < R ? (16 * qb + n16) % Lq : -(1 << 30);
         for (int j = d0 + wid; j < kv_end; j += kDecWaves) {
-            const char* const kr = kbase + (int64_t)j * krb;
-            const char* const vr = vbase + (int64_t)j * krb;
+            const int64_t joff = key_off(j);  // (paged: these keys may straddle a page boundary)
+            const char* const kr = kbase + joff;
+            const char* const vr = vbase + joff;
             u32x4 kq[NKS];
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) kq[ks] = *(const u32x4*)(kr + ks * 64 + g * 16);
@@ -424,18 +451,19 @@ __global__ __launch_bounds__(256) void fa_decode_combine_kernel(DecodeArgs a) {
     *(u32x2*)((unsigned short*)a.o + row * D + 4 * c4) = u32x2{pack2<T>(acc[0], acc[1]), pack2<T>(acc[2], acc[3])};
 }
 
-template <typename T, int D, int NQB>
+template <typename T, int D, int NQB, bool PAGED>
 static hipError_t launch_decode_one(const DecodeArgs& a, hipStream_t s) {
-    static const char* const names[3] = {"fa_decode_kernel<16 rows>", "fa_decode_kernel<32 rows>",
-                                         "fa_decode_kernel<64 rows>"};
+    static const char* const names[2][3] = {
+        {"fa_decode_kernel<16 rows>", "fa_decode_kernel<32 rows>", "fa_decode_kernel<64 rows>"},
+        {"fa_decode_kernel<16 rows, paged>", "fa_decode_kernel<32 rows, paged>", "fa_decode_kernel<64 rows, paged>"}};
     constexpr int lds = decode_lds_bytes(D);
     // (more than 64 KiB of dynamic LDS at d = 128: raise the kernel's limit once)
-    static const hipError_t attr = hipFuncSetAttribute((const void*)fa_decode_kernel<T, D, NQB>,
+    static const hipError_t attr = hipFuncSetAttribute((const void*)fa_decode_kernel<T, D, NQB, PAGED>,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (attr != hipSuccess) (void)hipGetLastError();
     const int64_t grid = (int64_t)a.B * a.Hkv * a.nsplit;
-    note_kernel(names[NQB == 1 ? 0 : NQB == 2 ? 1 : 2], grid);
-    hipLaunchKernelGGL((fa_decode_kernel<T, D, NQB>), dim3((unsigned)grid), dim3(kDecThreads), lds, s, a);
+    note_kernel(names[PAGED][NQB == 1 ? 0 : NQB == 2 ? 1 : 2], grid);
+    hipLaunchKernelGGL((fa_decode_kernel<T, D, NQB, PAGED>), dim3((unsigned)grid), dim3(kDecThreads), lds, s, a);
     if (hipError_t he = hipGetLastError()) return he;
     if (a.nsplit > 1) {
         const int64_t cgrid = ((int64_t)a.B * a.Hkv * a.R * (D / 4) + 255) / 256;
@@ -446,25 +474,33 @@ static hipError_t launch_decode_one(const DecodeArgs& a, hipStream_t s) {
     return hipSuccess;
 }
 
-template <typename T, int D>
+template <typename T, int D, bool PAGED>
 static hipError_t launch_decode_r(const DecodeArgs& a, hipStream_t s) {
-    if (a.R <= 16) return launch_decode_one<T, D, 1>(a, s);
-    if (a.R <= 32) return launch_decode_one<T, D, 2>(a, s);
-    return launch_decode_one<T, D, 4>(a, s);
+    if (a.R <= 16) return launch_decode_one<T, D, 1, PAGED>(a, s);
+    if (a.R <= 32) return launch_decode_one<T, D, 2, PAGED>(a, s);
+    return launch_decode_one<T, D, 4, PAGED>(a, s);
+}
+
+template <typename T, bool PAGED>
+static hipError_t launch_decode_d(int d, const DecodeArgs& a, hipStream_t s) {
+    if (d == 64) return launch_decode_r<T, 64, PAGED>(a, s);
+    if (d == 128) return launch_decode_r<T, 128, PAGED>(a, s);
+    return hipErrorInvalidValue;
 }
 
 template <typename T>
-static hipError_t launch_decode_d(int d, const DecodeArgs& a, hipStream_t s) {
-    if (d == 64) return launch_decode_r<T, 64>(a, s);
-    if (d == 128) return launch_decode_r<T, 128>(a, s);
-    return hipErrorInvalidValue;
+static hipError_t launch_decode_t(int d, const DecodeArgs& a, hipStream_t s) {
+    return a.block_table ? launch_decode_d<T, true>(d, a, s) : launch_decode_d<T, false>(d, a, s);
 }
 
 hipError_t launch_decode(Elem t, int d, const DecodeArgs& a, hipStream_t s) {
     if (a.R < 1 || a.R > kDecMaxRows || a.nsplit < 1 || a.kps % kDecBK || (a.nsplit > 1 && (!a.o_part || !a.lse)))
         return hipErrorInvalidValue;
-    if (t == Elem::BF16) return launch_decode_d<__bf16>(d, a, s);
-    if (t == Elem::F16) return launch_decode_d<_Float16>(d, a, s);
+    // paged: whole tiles per page (a tile's descriptor never straddles two blocks), a pool to clamp into
+    if (a.block_table && (a.page_size <= 0 || a.page_size % kDecBK || a.num_blocks <= 0 || a.table_stride <= 0))
+        return hipErrorInvalidValue;
+    if (t == Elem::BF16) return launch_decode_t<__bf16>(d, a, s);
+    if (t == Elem::F16) return launch_decode_t<_Float16>(d, a, s);
     return hipErrorInvalidValue;
 }
 

@@ -33,8 +33,16 @@ struct DecodeArgs {
     // nsplit > 1: normalised fp32 partial O [item][R][D] and base-2 lse [item][R] (-inf: empty)
     float* o_part;
     float* lse;
+    // paged cache (block_table != null): k / v are pools of num_blocks blocks of page_size keys,
+    // kv_stride is {block, head, row} and key j of batch b lives in block
+    // clamp(block_table[b * table_stride + j / page_size], 0, num_blocks - 1), row j % page_size
+    const int* block_table;
+    int64_t table_stride;
+    int page_size;        // a multiple of kDecBK: a tile never straddles two pages
+    int num_blocks;
 };
 
+// (a.block_table selects the paged kernels)
 hipError_t launch_decode(Elem t, int d, const DecodeArgs& a, hipStream_t s);
 
 }  // namespace fa

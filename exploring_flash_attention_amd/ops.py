@@ -13,8 +13,9 @@ Reference launchers these replace (tyler-utah/exploring_flash_attention):
   attention_v2       flash_attention_v2/CUDA/flash_attention_v2.h:438 (opt :559)
   attention_partial  partial_attention_kernel, flash_attention_v2/CUDA/flash_attention_v2.h:243
   combine            reduction_kernel,         flash_attention_v2/CUDA/flash_attention_v2.h:356
-attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV) has
-no counterpart in the reference.
+attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV) and
+attention_decode_paged (the same on a paged pool, through a block table) have no counterpart in
+the reference.
 """
 import contextlib
 import ctypes
@@ -580,6 +581,110 @@ def attention_decode(q, k, v, seqlens_k=None, causal=True, num_splits=None, out=
                                   None if workspace is None else _ptr(workspace),
                                   0 if workspace is None else workspace.numel() * workspace.element_size(),
                                   _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
+
+
+DECODE_PAGE_MULTIPLE = 64     # keys per page: a multiple of the decode kernel's key tile
+
+
+def attention_decode_paged(q, k_cache, v_cache, block_table, seqlens_k=None, max_seqlen_k=None, causal=True,
+                           num_splits=None, out=None, workspace=None):
+    """attention_decode on a paged KV cache, read in place through a block table
+    (fa_fwd_decode_paged): q ``[B, H, Lq, d]`` against pools k_cache, v_cache ``[num_blocks,
+    page_size, H_kv, d]``, bfloat16 or float16.  Key j of sequence b is row ``j % page_size`` of
+    block ``block_table[b, j // page_size]``; the result is exactly (bit for bit) attention_decode
+    on the cache gathered in table order, with the same ``seqlens_k``, ``causal``, ``num_splits``,
+    ``out`` and ``workspace`` (decode_plan with Lk = max_seqlen_k).
+
+    ``block_table``: int32 ``[B, P]`` on q's device, last dim contiguous, any row stride.  Only the
+    entries of pages that hold a key below len_b are read (the rest may be -1 or anything), and
+    every entry read is clamped to [0, num_blocks - 1] on the device: a corrupt table gives a
+    wrong result, never an access outside the pool.  ``max_seqlen_k`` (None: P * page_size): the
+    upper bound the lengths are clamped to and the split plan is made for; at most P * page_size.
+
+    The pool is never copied: any strides are taken when d is contiguous, k_cache and v_cache
+    share strides that are multiples of 8 elements and the bases are 16-byte aligned -- a
+    ``[num_blocks, H_kv, page_size, d]`` pool goes in as ``pool.transpose(1, 2)``.  Other views,
+    page_size not a multiple of 64, d other than 64 / 128 (no padding copy of a whole pool),
+    float64 and (H // H_kv) * Lq > 64 raise NotImplementedError.  q and out are small and copied
+    when not contiguous; with ``out`` and ``workspace`` given the call allocates nothing."""
+    _check_tensor("q", q, strided=True)
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16 or float16)")
+    _check_tensor("k_cache", k_cache, q.dtype, q.device, strided=True)
+    _check_tensor("v_cache", v_cache, q.dtype, q.device, strided=True)
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must have the same shape")
+    if q.shape[3] != k_cache.shape[3]:
+        raise ValueError(f"q {tuple(q.shape)} and k_cache {tuple(k_cache.shape)} disagree on d")
+    B, H, Lq, d = q.shape
+    nblk, ps, Hkv = k_cache.shape[:3]
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"attention_decode_paged: H={H} query heads are not a multiple of H_kv={Hkv} K/V heads")
+    if q.dtype == torch.float64:
+        raise NotImplementedError("attention_decode_paged: float64 tensors are not supported (use bfloat16 or float16)")
+    if d not in DECODE_HEAD_DIMS:
+        raise NotImplementedError(f"attention_decode_paged: head dim d={d} is not supported (64 or 128; a pool is "
+                                  "not padded)")
+    if ps <= 0 or ps % DECODE_PAGE_MULTIPLE:
+        raise NotImplementedError(f"attention_decode_paged: page_size={ps} is not a multiple of {DECODE_PAGE_MULTIPLE} "
+                                  "keys (pages of 16 / 32 keys have no kernel)")
+    if (H // Hkv) * Lq > DECODE_MAX_ROWS:
+        raise NotImplementedError(f"attention_decode_paged: (H / H_kv) * Lq = {H // Hkv} * {Lq} packed query rows exceed "
+                                  f"{DECODE_MAX_ROWS}; long queries are served by attention_v1")
+    _check_tensor("block_table", block_table, torch.int32, q.device, ndim=2, strided=True)
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError(f"block_table must be an int32 tensor of shape ({B}, pages), got {block_table.dtype} "
+                         f"{tuple(block_table.shape)}")
+    P = block_table.shape[1]
+    if (P > 1 and block_table.stride(1) != 1) or (B > 1 and block_table.stride(0) < P):
+        raise ValueError(f"block_table rows must be contiguous and at least {P} entries apart (strides "
+                         f"{tuple(block_table.stride())})")
+    Lk = P * ps if max_seqlen_k is None else int(max_seqlen_k)
+    if Lk < 0:
+        raise ValueError(f"max_seqlen_k={Lk} must not be negative")
+    if Lk > P * ps:
+        raise ValueError(f"max_seqlen_k={Lk} exceeds what the block table maps ({P} pages of {ps} keys)")
+    if seqlens_k is not None:
+        _check_tensor("seqlens_k", seqlens_k, torch.int32, q.device, ndim=1)
+        if seqlens_k.dtype != torch.int32 or tuple(seqlens_k.shape) != (B,):
+            raise ValueError(f"seqlens_k must be an int32 tensor of shape ({B},), got {seqlens_k.dtype} "
+                             f"{tuple(seqlens_k.shape)}")
+    st = k_cache.stride()
+    if nblk > 0 and not (st == v_cache.stride() and st[3] == 1 and all(x > 0 and x % 8 == 0 for x in st[:3])
+                         and st[1] >= d and st[1] <= 1 << 20 and k_cache.data_ptr() % 16 == 0
+                         and v_cache.data_ptr() % 16 == 0):
+        raise NotImplementedError(f"attention_decode_paged: the pool is read in place and this view cannot be "
+                                  f"addressed (k_cache strides {tuple(st)}, v_cache strides {tuple(v_cache.stride())}): "
+                                  "d contiguous, shared strides that are multiples of 8 elements, 16-byte aligned bases")
+    ns = 0 if num_splits is None else int(num_splits)
+    if ns < 0:
+        raise ValueError(f"num_splits={ns} must be positive (or None)")
+    o = _out(out, q, strided=True)
+    if q.numel() == 0:
+        return o
+    if Lk == 0:  # no keys: every row is empty
+        return o.zero_()
+    if nblk == 0:
+        raise ValueError("attention_decode_paged: the pool has no blocks")
+    qp = q.contiguous()
+    op = o if o.is_contiguous() else torch.empty((B, H, Lq, d), dtype=q.dtype, device=q.device)
+    nbytes = decode_plan(B, H, Hkv, Lq, Lk, d, ns, q.dtype)[2]
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    else:
+        _check_tensor("workspace", workspace, torch.uint8, q.device, ndim=1)
+        if workspace.numel() * workspace.element_size() < nbytes:
+            raise ValueError(f"workspace too small: {nbytes} bytes needed")
+    # {block, head, row} of the [num_blocks, page_size, H_kv, d] view
+    cst = (ctypes.c_int64 * 3)(st[0], st[2], st[1])
+    _launched(lib().fa_fwd_decode_paged(_ptr(qp), _ptr(k_cache), _ptr(v_cache), _ptr(op), _ptr(block_table),
+                                        None if seqlens_k is None else _ptr(seqlens_k), B, H, Hkv, Lq, Lk, d, nblk, ps,
+                                        block_table.stride(0) if B > 1 else max(P, block_table.stride(0)), cst,
+                                        1.0 / d ** 0.5, _lib.FA_FWD_CAUSAL if causal else 0, ns,
+                                        None if workspace is None else _ptr(workspace),
+                                        0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                        _DTYPES[q.dtype], _stream(q)))
     return _unpad_into(op, o, d)
 
 

@@ -85,7 +85,8 @@ typedef enum fa_dtype {
  *          fa_fwd_v1_causal added later under the same number (an addition only: callers built
  *          against 0.4 stay valid; a library without it fails to resolve the symbol);
  *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way; then fa_fwd_decode_plan and
- *          fa_fwd_decode (KV-cache decode), again additions only.
+ *          fa_fwd_decode (KV-cache decode), again additions only; then fa_fwd_decode_paged (the
+ *          same forward through a block table), an addition only.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -370,6 +371,47 @@ int fa_fwd_decode(const void* q, const void* k, const void* v, void* o, const in
                   int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
                   const int64_t* kv_strides, double softmax_scale, unsigned flags, int num_splits,
                   void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ---- Paged KV-cache decode: fa_fwd_decode on a cache kept in fixed-size pages of a shared pool ----
+ *
+ * fa_fwd_decode_paged computes exactly what fa_fwd_decode computes on the cache obtained by
+ * gathering each sequence's pages in table order, and reads the pool in place.  Key j of batch b,
+ * K/V head hkv lives at (elements, d contiguous; the same rule for k_cache and v_cache)
+ *     blk  = block_table[b * table_stride + j / page_size]
+ *     addr = cache + blk * stride_block + hkv * stride_head + (j % page_size) * stride_row
+ * q, o, seqlens_k, flags, softmax_scale, num_splits, the workspace, the split plan, the combine
+ * kernel and the bitwise repeatability are fa_fwd_decode's, unchanged.
+ *   Lk: the caller's upper bound on the lengths (max_seqlen_k), len_b = seqlens_k[b] clamped to
+ *     [0, Lk]; it need not be a multiple of page_size.  The plan and the workspace are those of
+ *     fa_fwd_decode_plan(B, H, H_kv, Lq, Lk, d, ...): a table wider than ceil(Lk / page_size)
+ *     does not add splits.
+ *   block_table: int32 in DEVICE memory, row b at block_table + b * table_stride, table_stride >=
+ *     ceil(Lk / page_size).  The kernel reads it itself (no host read, no synchronisation).
+ *   page_size: keys per page, a positive multiple of 64 (128, 192, 256, ...: any multiple), so
+ *     that every 64-key tile of the kernel lies inside one page.  Pages of 16 or 32 keys are not
+ *     supported.
+ *   num_blocks: blocks of the pool.  Every table entry the kernel uses is clamped to
+ *     [0, num_blocks - 1] before it enters an address: a corrupt entry gives a wrong result for
+ *     that sequence, never an access outside the pool.
+ *   cache_strides: {block, head, row} element strides shared by k_cache and v_cache, NULL for a
+ *     contiguous [num_blocks, page_size, H_kv, d] pool ({page_size*H_kv*d, d, H_kv*d}); a
+ *     [num_blocks, H_kv, page_size, d] pool is {H_kv*page_size*d, page_size*d, d}.  Positive
+ *     multiples of 8, row stride >= d and <= 2^20.
+ * What is read: of the table, only the entries of pages that hold a key below len_b (entries
+ * past that may be -1 or anything else); of the pool, only rows of keys below len_b in the blocks
+ * those entries name -- unused blocks, the rest of a last page and pages beyond len_b may hold
+ * anything (NaN included).  Keys behind the causal mask contribute nothing, as in fa_fwd_decode.
+ * FA_ERR_INVALID_ARG: fa_fwd_decode's, a NULL or misaligned block_table, num_blocks <= 0,
+ * page_size <= 0, table_stride < ceil(Lk / page_size), bad strides.  FA_ERR_UNSUPPORTED:
+ * fa_fwd_decode's, page_size not a multiple of 64, a row stride above 2^20.
+ * fa_last_kernels: "fa_decode_kernel<16|32|64 rows, paged> [grid B*H_kv*splits]", then the
+ * combine kernel as above. */
+int fa_fwd_decode_paged(const void* q, const void* k_cache, const void* v_cache, void* o,
+                        const int32_t* block_table, const int32_t* seqlens_k,
+                        int64_t B, int64_t H, int64_t H_kv, int64_t Lq, int64_t Lk, int64_t d,
+                        int64_t num_blocks, int64_t page_size, int64_t table_stride,
+                        const int64_t* cache_strides, double softmax_scale, unsigned flags, int num_splits,
+                        void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
