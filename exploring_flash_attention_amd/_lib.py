@@ -26,7 +26,7 @@ FA_DTYPE_FP16_SCALED = 4  # split-KV partials: fp16 scaled per row by a power of
 FA_KV_TILES_AUTO = -1  # kv_tiles_per_block: split chosen from the device's occupancy
 FA_BLOCKS_PER_WG_AUTO = 0  # blocks_per_workgroup: the library groups the key blocks itself
 FA_V2_COUNTERS_ZERO = 1  # fa_fwd_v2_ex2: the caller vouches that the workspace counters are zero
-FA_FWD_CAUSAL = 1  # fa_fwd_v1_gqa flags: row i attends to keys 0..i (fa_fwd_decode: bottom-right aligned)
+FA_FWD_CAUSAL = 1  # fa_fwd_v1_gqa / fa_fwd_varlen flags: row i attends to keys 0..i (fa_fwd_decode: bottom-right aligned)
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -44,6 +44,8 @@ SIGNATURES = {
     "fa_fwd_v1_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_causal": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_gqa": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, ctypes.c_double, ctypes.c_uint, _I, _P]),
+    "fa_fwd_varlen": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double,
+                           ctypes.c_uint, _I, _P]),
     "fa_fwd_v1_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_tiled_d": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
     "fa_fwd_v1_tiled_d_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, ctypes.c_double, _I, _P]),

@@ -500,6 +500,81 @@ int fa_fwd_v1_gqa(const void* q, const void* k, const void* v, void* o, int64_t 
     return ok();
 }
 
+int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens, int64_t B,
+                  int64_t total_tokens, int64_t max_seqlen, int64_t H, int64_t H_kv, int64_t d,
+                  const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
+                  double softmax_scale, unsigned flags, int dtype, void* stream) {
+    fa::Elem e;
+    if (flags & ~FA_FWD_CAUSAL)
+        return fail(FA_ERR_INVALID_ARG, "varlen: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
+    if (B <= 0) return fail(FA_ERR_INVALID_ARG, "varlen: B=%lld must be positive", (long long)B);
+    if (total_tokens < 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: total_tokens=%lld must not be negative", (long long)total_tokens);
+    if (max_seqlen <= 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: max_seqlen=%lld must be positive", (long long)max_seqlen);
+    if (H <= 0 || d <= 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: H=%lld and d=%lld must be positive", (long long)H, (long long)d);
+    if (H_kv <= 0 || H_kv > H || H % H_kv != 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: H_kv=%lld must be positive and divide H=%lld", (long long)H_kv,
+                    (long long)H);
+    if (!supported_d(d))
+        return fail(FA_ERR_UNSUPPORTED, "varlen: head dim d=%lld has no varlen kernel (32, 64, 128, 256 only)",
+                    (long long)d);
+    if (int st = check_dtype(dtype, &e)) return st;
+    if (e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "varlen: FA_DTYPE_FP64 has no varlen kernel (bf16 / fp16 only)");
+    if (int st = check_ptrs(q, k, v, o)) return st;
+    if (!cu_seqlens || ((uintptr_t)cu_seqlens & 3))
+        return fail(FA_ERR_INVALID_ARG, "varlen: cu_seqlens must be non-null and 4-byte aligned");
+    if (total_tokens > (int64_t)0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "varlen: total_tokens=%lld exceeds 2^31-1 (cu_seqlens is int32)",
+                    (long long)total_tokens);
+    // (a length beyond the tokens is clamped on the device anyway: the grid need not cover it)
+    const int64_t msl = max_seqlen < total_tokens ? max_seqlen : total_tokens;
+    const int64_t nqt = (msl + fa::kBQ - 1) / fa::kBQ;
+    if (B > (int64_t)0x7fffffff || H > (int64_t)0x7fffffff || B * H >= (int64_t)1 << 31 ||
+        B * H * (nqt > 0 ? nqt : 1) >= (int64_t)1 << 31)
+        return fail(FA_ERR_UNSUPPORTED, "varlen: grid of B * H * ceil(max_seqlen / %d) = %lld * %lld * %lld workgroups "
+                    "exceeds 2^31-1", fa::kBQ, (long long)B, (long long)H, (long long)nqt);
+    const int64_t contig_q[2] = {H * d, d}, contig_kv[2] = {H_kv * d, d};
+    const int64_t* st[3] = {q_strides ? q_strides : contig_q, kv_strides ? kv_strides : contig_kv,
+                            o_strides ? o_strides : contig_q};
+    const char* names[3] = {"q", "k/v", "o"};
+    for (int t = 0; t < 3; ++t) {
+        for (int i = 0; i < 2; ++i)
+            if (st[t][i] <= 0 || st[t][i] % 8)
+                return fail(FA_ERR_INVALID_ARG, "varlen: %s stride[%d]=%lld must be positive and a multiple of 8 elements",
+                            names[t], i, (long long)st[t][i]);
+        if (st[t][0] < d)
+            return fail(FA_ERR_INVALID_ARG, "varlen: %s token stride %lld < d=%lld", names[t], (long long)st[t][0],
+                        (long long)d);
+        // (a tile's descriptor spans at most 128 rows: 32-bit offsets hold with room to spare)
+        if (st[t][0] > (int64_t)1 << 20)
+            return fail(FA_ERR_UNSUPPORTED, "varlen: %s token stride %lld exceeds 2^20 elements", names[t],
+                        (long long)st[t][0]);
+    }
+    fa::FwdArgs a = base_args(q, k, v, o, B * H, msl, msl, d, e);
+    if (int s2 = apply_scale(a, softmax_scale)) return s2;
+    if (total_tokens == 0) {  // no rows: nothing to launch
+        kernels_begin();
+        return ok();
+    }
+    a.nqt = (int)nqt;
+    a.H = H;
+    a.kv_group = (int)(H / H_kv);
+    a.strided = 1;
+    a.q_stride[2] = st[0][0]; a.q_stride[1] = st[0][1];
+    a.k_stride[2] = st[1][0]; a.k_stride[1] = st[1][1];
+    a.o_stride[2] = st[2][0]; a.o_stride[1] = st[2][1];
+    a.cu_seqlens = cu_seqlens;
+    a.max_seqlen = (int)msl;
+    a.total_rows = total_tokens;
+    kernels_begin();
+    if (hipError_t he = fa::launch_fwd_varlen(e, (int)d, (flags & FA_FWD_CAUSAL) != 0, a, (hipStream_t)stream))
+        return hip_fail(he, "fa_fwd_varlen launch");
+    return ok();
+}
+
 int fa_fwd_v1_tiled_d(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
                       int64_t L, int64_t d, int d_tile_qk, int d_tile_v, int dtype, void* stream) {
     return fa_fwd_v1_tiled_d_scaled(q, k, v, o, B, H, L, d, d_tile_qk, d_tile_v,

@@ -1,6 +1,7 @@
 // fa_fwd_kernel.hpp -- flash-attention forward kernel for MI355X (gfx950 / CDNA4), included by
-// fa_fwd.hip (contiguous [B,H,L,d] launches), fa_fwd_strided.hip (strided launches) and
-// fa_fwd_causal.hip (the causal instantiations).
+// fa_fwd.hip (contiguous [B,H,L,d] launches), fa_fwd_strided.hip (strided launches),
+// fa_fwd_causal.hip (the causal instantiations), fa_fwd_gqa.hip (grouped-query) and
+// fa_fwd_varlen.hip (token-packed ragged batches).
 //
 // One kernel template serves the three reference kernel families:
 //   final mode   (MODE=kFinal): FA-v1 fused / d-tiled forward
@@ -106,11 +107,18 @@ namespace fa {
 // query tiles of a head are handed out longest first.  Everything else is the non-causal kernel.
 // GQA (final mode, contiguous, causal or not; instantiated in fa_fwd_gqa.hip): K and V hold
 // BH / a.kv_group heads and query head b*h reads head b*h / kv_group -- only the K / V base moves.
+// VARLEN (final mode, TAIL, STRIDED and GQA set, causal or not; instantiated in fa_fwd_varlen.hip):
+// token-packed [T, H, d] q / o and [T, H_kv, d] k / v with element strides {token, head} in
+// a.{q,k,o}_stride[2], [1].  A work item is (sequence b, head, query tile); its row offset and
+// length come from a.cu_seqlens on the device, clamped so that no descriptor and no store can
+// leave rows [0, T), and stand in for a.Lq / a.Lk.  An item whose tile starts past the length
+// returns before any barrier or DMA.  MHA runs with kv_group = 1.
 template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false,
-          bool GQA = false>
+          bool GQA = false, bool VARLEN = false>
 __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void fa_fwd_kernel(FwdArgs a) {
-    static_assert(!CAUSAL || (MODE == kFinal && !STRIDED), "causal: final mode, contiguous tensors");
-    static_assert(!GQA || (MODE == kFinal && !STRIDED), "GQA: final mode, contiguous tensors");
+    static_assert(!CAUSAL || (MODE == kFinal && (!STRIDED || VARLEN)), "causal: final mode, contiguous tensors");
+    static_assert(!GQA || (MODE == kFinal && (!STRIDED || VARLEN)), "GQA: final mode, contiguous tensors");
+    static_assert(!VARLEN || (MODE == kFinal && TAIL && STRIDED && GQA), "varlen: final mode, runtime lengths, strided rows");
     using M = Mma<T>;
     using v8 = typename M::v8;
     constexpr int RB = kRB;                   // 32-row query blocks per wave
@@ -148,6 +156,25 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     } else {
         decode_item(a, w, qt, split, bh);
     }
+    // VARLEN: bh = b * H + head.  Tokens [start, start + len) of the packed tensors are this
+    // sequence's rows: start = clamp(cu[b], 0, T), len = clamp(cu[b+1] - start, 0, min(max_seqlen,
+    // T - start)) -- whatever cu_seqlens holds, start + len <= T.  (Scalar loads: b is uniform.
+    // readfirstlane: every descriptor word below derives from these two, see dma_tile.)
+    int vl_start = 0, vl_len = 0, vl_head = 0;
+    if constexpr (VARLEN) {
+        const unsigned b = (unsigned)bh / (unsigned)a.H;
+        vl_head = (int)((unsigned)bh - b * (unsigned)a.H);
+        const int64_t nt = a.total_rows;  // T
+        const int64_t c0 = a.cu_seqlens[b], c1 = a.cu_seqlens[b + 1];
+        const int64_t st = c0 < 0 ? 0 : c0 > nt ? nt : c0;
+        const int64_t room = nt - st < a.max_seqlen ? nt - st : a.max_seqlen;
+        const int64_t n = c1 - st;
+        vl_start = __builtin_amdgcn_readfirstlane((int)st);
+        vl_len = __builtin_amdgcn_readfirstlane((int)(n < 0 ? 0 : n > room ? room : n));
+        // no row of this tile exists (a short or empty sequence): uniform exit, nothing touched
+        if ((int64_t)qt * kBQ >= vl_len) return;
+    }
+    const int64_t Lq = VARLEN ? vl_len : a.Lq, Lk = VARLEN ? vl_len : a.Lk;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -166,23 +193,29 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int64_t kv_begin = (int64_t)split * a.kv_per_split;
     // (causal: the keys up to the query tile's last row -- a multiple of the KV tile unless it
     // is Lk itself, where the partial-last-tile path applies as ever)
-    const int64_t kv_end = CAUSAL ? ((int64_t)(qt + 1) * kBQ < a.Lk ? (int64_t)(qt + 1) * kBQ : a.Lk)
-                           : kv_begin + a.kv_per_split < a.Lk ? kv_begin + a.kv_per_split : a.Lk;
+    const int64_t kv_end = CAUSAL ? ((int64_t)(qt + 1) * kBQ < Lk ? (int64_t)(qt + 1) * kBQ : Lk)
+                           : VARLEN ? Lk
+                           : kv_begin + a.kv_per_split < Lk ? kv_begin + a.kv_per_split : Lk;
     const int nkv = (int)(kv_end - kv_begin);
     const int ntiles = (nkv + kBK - 1) / kBK;
 
     // row strides in bytes (compile-time ROWB for contiguous tensors) and head bases
     const int qrb = STRIDED ? (int)(a.q_stride[2] * 2) : ROWB;
     const int krb = STRIDED ? (int)(a.k_stride[2] * 2) : ROWB;
-    const int64_t hb = STRIDED ? bh / a.H : 0, hh = STRIDED ? bh - hb * a.H : 0;
-    const int64_t q_head = STRIDED ? hb * a.q_stride[0] + hh * a.q_stride[1] : bh * a.Lq * D;
-    int64_t k_head = STRIDED ? hb * a.k_stride[0] + hh * a.k_stride[1] : bh * a.Lk * D;
-    if constexpr (GQA) k_head = gqa_kv_head(a, bh) * a.Lk * D;
+    // (varlen: the sequence's first token row and the head; K/V head = head / kv_group)
+    const int64_t hb = STRIDED && !VARLEN ? bh / a.H : 0, hh = VARLEN ? vl_head : STRIDED ? bh - hb * a.H : 0;
+    const int64_t q_head = VARLEN    ? vl_start * a.q_stride[2] + hh * a.q_stride[1]
+                           : STRIDED ? hb * a.q_stride[0] + hh * a.q_stride[1]
+                                     : bh * a.Lq * D;
+    int64_t k_head = VARLEN    ? vl_start * a.k_stride[2] + (int64_t)((unsigned)vl_head / (unsigned)a.kv_group) * a.k_stride[1]
+                     : STRIDED ? hb * a.k_stride[0] + hh * a.k_stride[1]
+                               : bh * a.Lk * D;
+    if constexpr (GQA && !VARLEN) k_head = gqa_kv_head(a, bh) * a.Lk * D;
     // Q descriptor over this workgroup's query tile only, so that its 32-bit offsets stay
     // small however long the sequence (rows past Lq read zeros)
     const int64_t q_tile0 = (int64_t)qt * kBQ;
     const unsigned short* Qh = (const unsigned short*)a.q + q_head + q_tile0 * (qrb / 2);
-    const int64_t q_rows = a.Lq - q_tile0 < kBQ ? a.Lq - q_tile0 : kBQ;
+    const int64_t q_rows = Lq - q_tile0 < kBQ ? Lq - q_tile0 : kBQ;
     const __amdgpu_buffer_rsrc_t qrs = make_rsrc(Qh, STRIDED ? (q_rows - 1) * qrb + ROWB : q_rows * ROWB);
     // K/V of this split; a tile's descriptor (made per DMA, scalar arithmetic only) starts
     // at the tile and ends at the split's last key, so the hardware range check -- which
@@ -772,7 +805,9 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
 
     FA_STAMP(3);
     // output row base (final O; the fused split mode's o_final)
-    const int64_t o_head = STRIDED ? hb * a.o_stride[0] + hh * a.o_stride[1] : bh * a.Lq * D;
+    const int64_t o_head = VARLEN    ? vl_start * a.o_stride[2] + hh * a.o_stride[1]
+                           : STRIDED ? hb * a.o_stride[0] + hh * a.o_stride[1]
+                                     : bh * a.Lq * D;
     const int64_t orow = STRIDED ? a.o_stride[2] : D;
     // ---- epilogue: lane holds O^T[dv][q_row] for dv = 32*db + (i&3) + 8*(i>>2) + 4*hf
     // store v * scale as one 16-bit output row (row base Oh).  Column groups g and g+1 of a
@@ -977,7 +1012,7 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         const int64_t q_row = q_row0 + 32 * r;
         const float l_tot = row_sum(r);
         float inv = 1.f / l_tot;
-        if (q_row >= a.Lq) continue;
+        if (q_row >= Lq) continue;
         if constexpr (MODE == kFinal) {
             store_row((unsigned short*)a.o + o_head + q_row * orow, o[r], inv);
         } else {

@@ -90,6 +90,13 @@ struct FwdArgs {
     // fused split mode, fa_fwd16_kernel: arrival counted before the partial stores, so that the
     // last arriver never stores its own (fa_fwd16_kernel.hpp); 0: stores first
     int arrive_first;
+    // varlen (fa_fwd_varlen.hip; final mode, token-packed [T, H, d] tensors, Lq = Lk per sequence):
+    // cu_seqlens is int32 [B + 1] on the device, sequence b owns token rows [cu[b], cu[b+1]) of
+    // q, k, v and o; BH = B * H, nqt = ceil(max_seqlen / kBQ), total_rows = T.  The strides'
+    // [2] is the token stride, [1] the head stride, [0] unused.  (Appended: no field moved.)
+    const int* cu_seqlens;
+    int max_seqlen;
+    int64_t total_rows;
 };
 
 // (query tile, split, b*h) of work item w (after xcd_remap)
@@ -166,6 +173,9 @@ hipError_t launch_fwd_causal(Elem t, int d, const FwdArgs& a, hipStream_t s);
 // the GQA forward (fa_fwd_gqa.hip): final mode, contiguous, one split, bf16 / fp16, a.kv_group > 1;
 // causal or not, on the kernel family launch_fwd / launch_fwd_causal pick for the same B*H, L, d
 hipError_t launch_fwd_gqa(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
+// the varlen forward (fa_fwd_varlen.hip): final mode, token-packed strided tensors, device-side
+// cu_seqlens, bf16 / fp16, causal or not, a.kv_group >= 1 (1 = MHA)
+hipError_t launch_fwd_varlen(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
 int fwd_lds_bytes(int d);
 // compute units of the device that owns `s` (the current device for the null stream;
 // fa_capi.cpp; 256 without a device)

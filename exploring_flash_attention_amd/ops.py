@@ -13,9 +13,10 @@ Reference launchers these replace (tyler-utah/exploring_flash_attention):
   attention_v2       flash_attention_v2/CUDA/flash_attention_v2.h:438 (opt :559)
   attention_partial  partial_attention_kernel, flash_attention_v2/CUDA/flash_attention_v2.h:243
   combine            reduction_kernel,         flash_attention_v2/CUDA/flash_attention_v2.h:356
-attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV) and
-attention_decode_paged (the same on a paged pool, through a block table) have no counterpart in
-the reference.
+attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV),
+attention_decode_paged (the same on a paged pool, through a block table) and attention_varlen
+(ragged prefill batches: token-packed [T, H, d] tensors with a device-side cu_seqlens) have no
+counterpart in the reference.
 """
 import contextlib
 import ctypes
@@ -271,6 +272,101 @@ def attention_v1(q, k, v, out=None, causal=False):
     op = torch.empty((B, H, L, D), dtype=q.dtype, device=q.device)
     _launched(lib().fa_fwd_v1_scaled(_ptr(qp), _ptr(kp), _ptr(vp), _ptr(op), B, H, L, D, 1.0 / d ** 0.5,
                                  _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
+
+
+VARLEN_MAX_TOKEN_STRIDE = 1 << 20  # elements between token rows the varlen kernel addresses in place
+
+
+def _varlen_strides(ts, d):
+    """{token, head} element strides of [T, H, d] tensors the varlen kernel can address in place,
+    or None: d contiguous, strides positive multiples of 8 elements, token stride >= d and within
+    VARLEN_MAX_TOKEN_STRIDE, 16-byte aligned base."""
+    for t in ts:
+        st = t.stride()
+        if not (st[2] == 1 and st[0] > 0 and st[1] > 0 and st[0] % 8 == 0 and st[1] % 8 == 0 and st[0] >= d
+                and st[0] <= VARLEN_MAX_TOKEN_STRIDE and t.data_ptr() % 16 == 0):
+            return None
+    return tuple((ctypes.c_int64 * 2)(*t.stride()[:2]) for t in ts)
+
+
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
+    """Variable-length (token-packed) self-attention, one launch for a ragged batch
+    (fa_fwd_varlen): q ``[T, H, d]``, k and v ``[T, H_kv, d]``, bfloat16 or float16, H a multiple
+    of H_kv (query head h reads K/V head h // (H // H_kv)).  ``cu_seqlens``: int32 ``[B + 1]`` on
+    q's device; sequence b owns token rows ``cu_seqlens[b] : cu_seqlens[b+1]`` of q, k, v and the
+    output, and attends to its own keys only -- all of them, or with ``causal=True`` those up to
+    the token's own position.  Returns ``[T, H, d]``.
+
+    cu_seqlens is never read on the host (no synchronisation); the device clamps every offset and
+    length to the T rows and to ``max_seqlen``, so a corrupt array gives a wrong result, never an
+    access outside the tensors.  ``max_seqlen`` is an upper bound of the lengths: it sizes the grid
+    (B * H * ceil(max_seqlen / 128) workgroups, those past a sequence's end exit at once) and a
+    longer sequence is truncated to it.  Rows of the output that belong to no sequence -- past
+    ``cu_seqlens[-1]``, or past ``max_seqlen`` inside a sequence -- are left untouched.
+
+    q, k, v and out are read and written in place when d is contiguous, the token and head
+    strides are multiples of 8 elements (token stride at most 2**20), k and v share strides and
+    the bases are 16-byte aligned -- e.g. the three slices of a fused ``[T, (H + 2 H_kv) * d]``
+    QKV projection viewed as ``[T, heads, d]``; other views are copied.
+
+    d = 32, 64, 128 and 256 run natively; any other d <= 256 is zero-padded to the next of them
+    with the scale 1/sqrt(d) kept -- that COPIES q, k and v on every call: a convenience, not a
+    fast path.  d > 256 and float64 raise NotImplementedError."""
+    # (shapes and dtypes first, so that a malformed call is named as such wherever its tensors live)
+    for name, t in (("q", q), ("k", k), ("v", v), ("cu_seqlens", cu_seqlens)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be 3-D [tokens, heads, d], got shape {tuple(t.shape)}")
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16 or float16)")
+    if k.shape != v.shape:
+        raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} must have the same shape")
+    if q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on the tokens T or d")
+    T, H, d = q.shape
+    Hkv = k.shape[1]
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"attention_varlen: H={H} query heads are not a multiple of H_kv={Hkv} K/V heads")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1:
+        raise ValueError(f"cu_seqlens must be an int32 tensor of shape (B + 1,), got {cu_seqlens.dtype} "
+                         f"{tuple(cu_seqlens.shape)}")
+    _check_tensor("q", q, ndim=3, strided=True)
+    _check_tensor("k", k, q.dtype, q.device, ndim=3, strided=True)
+    _check_tensor("v", v, q.dtype, q.device, ndim=3, strided=True)
+    _check_tensor("cu_seqlens", cu_seqlens, torch.int32, q.device, ndim=1)
+    B = cu_seqlens.numel() - 1
+    max_seqlen = int(max_seqlen)
+    if max_seqlen < 0:
+        raise ValueError(f"max_seqlen={max_seqlen} must not be negative")
+    if q.dtype == torch.float64:
+        raise NotImplementedError("attention_varlen: float64 tensors are not supported (use bfloat16 or float16)")
+    if d > 256:
+        raise NotImplementedError(f"attention_varlen: head dim d={d} is not supported (1 <= d <= 256)")
+    o = _out(out, q, strided=True)
+    if q.numel() == 0 or B == 0 or max_seqlen == 0:  # no rows, no sequences: nothing to launch
+        return o
+    D = kernel_head_dim(d)
+    if D != d:
+        q, k, v = (_pad_d(t, D) for t in (q, k, v))
+    st = _varlen_strides((q, k, o), D) if D == d and k.stride() == v.stride() else None
+    if st is None:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if D != d or _varlen_strides((o,), D) is None:
+            # rows of no sequence keep what out holds: the kernel's output starts as a copy of it
+            op = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
+            if out is not None:
+                op[..., :d].copy_(o)
+        else:
+            op = o
+        st = _varlen_strides((q, k, op), D)
+    else:
+        op = o
+    _launched(lib().fa_fwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(op), _ptr(cu_seqlens), B, T, max_seqlen, H, Hkv, D,
+                                  st[0], st[1], st[2], 1.0 / d ** 0.5, _lib.FA_FWD_CAUSAL if causal else 0,
+                                  _DTYPES[q.dtype], _stream(q)))
     return _unpad_into(op, o, d)
 
 

@@ -86,7 +86,8 @@ typedef enum fa_dtype {
  *          against 0.4 stay valid; a library without it fails to resolve the symbol);
  *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way; then fa_fwd_decode_plan and
  *          fa_fwd_decode (KV-cache decode), again additions only; then fa_fwd_decode_paged (the
- *          same forward through a block table), an addition only.
+ *          same forward through a block table), an addition only; then fa_fwd_varlen (token-packed
+ *          ragged batches through a device-side cu_seqlens), an addition only.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -156,6 +157,36 @@ int fa_fwd_v1_causal(const void* q, const void* k, const void* v, void* o,
 #define FA_FWD_CAUSAL 1u
 int fa_fwd_v1_gqa(const void* q, const void* k, const void* v, void* o,
                   int64_t B, int64_t H, int64_t H_kv, int64_t L, int64_t d,
+                  double softmax_scale, unsigned flags, int dtype, void* stream);
+/* Variable-length (token-packed) self-attention: one launch for a ragged batch, no padding.
+ * q and o are [total_tokens, H, d], k and v [total_tokens, H_kv, d] (H a multiple of H_kv, query
+ * head h reads K/V head h / (H / H_kv)); cu_seqlens is an int32 [B + 1] array ON THE DEVICE and
+ * sequence b owns token rows [cu_seqlens[b], cu_seqlens[b+1]) of all four tensors.  For token i
+ * of sequence b at position p = i - cu_seqlens[b],
+ *   O[i, h] = softmax(softmax_scale * Q[i, h] K[cu[b] .. cu[b] + n, h / G]^T) V[cu[b] .. cu[b] + n, h / G]
+ * with n = the sequence's length, or p + 1 with FA_FWD_CAUSAL; sequences never see each other's
+ * keys.  The lengths are read on the device only (no host read, no synchronisation), clamped:
+ *   start_b = clamp(cu[b], 0, total_tokens),
+ *   len_b   = clamp(cu[b+1] - start_b, 0, min(max_seqlen, total_tokens - start_b)),
+ * so a corrupt or non-monotonic cu_seqlens gives a wrong result, never an access outside q, k, v
+ * or o.  Rows of o that belong to no sequence (past cu[B], or past max_seqlen inside a sequence)
+ * are never written; a zero-length sequence costs workgroups that exit at once.
+ *   q_strides, kv_strides (shared by k and v), o_strides: two element strides {token, head} each,
+ *     d contiguous, or NULL for contiguous [total_tokens, H, d] -- a slice of a fused
+ *     [total_tokens, (H + 2 H_kv) d] QKV projection is {(H + 2 H_kv) d, d}, read in place.
+ *     Positive multiples of 8 elements, token stride >= d and <= 2^20; bases 16-byte aligned.
+ *   flags: 0 or FA_FWD_CAUSAL (other bits: FA_ERR_INVALID_ARG, the message names "flags").
+ *   max_seqlen: an upper bound of the lengths (longer sequences are truncated to it); the grid
+ *     is B * H * ceil(max_seqlen / 128) workgroups and must stay below 2^31 (FA_ERR_UNSUPPORTED,
+ *     "grid").
+ * FA_ERR_INVALID_ARG: a null pointer (cu_seqlens included) or misaligned one, H_kv not dividing
+ * H, B <= 0, max_seqlen <= 0, total_tokens < 0, a scale that is not positive and finite, bad
+ * strides.  FA_ERR_UNSUPPORTED: d outside {32, 64, 128, 256}, FA_DTYPE_FP64 (the message names
+ * "varlen"), total_tokens > 2^31 - 1.  total_tokens == 0 returns FA_OK without a launch.
+ * fa_last_kernels: "fa_fwd_kernel<final, varlen[, causal][, gqa]>" with its grid. */
+int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens,
+                  int64_t B, int64_t total_tokens, int64_t max_seqlen, int64_t H, int64_t H_kv, int64_t d,
+                  const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
                   double softmax_scale, unsigned flags, int dtype, void* stream);
 /* fa_fwd_v1_scaled on strided tensors.  q_strides, kv_strides (shared by k and v) and
  * o_strides each point to three element strides {batch, head, row} of a [B, H, L, d] view
