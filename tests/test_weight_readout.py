@@ -62,11 +62,46 @@ a late query tile: (1) in row 383 alone passes it in bf16 (0.73 of its bound; fp
 still sees that 1.5e-3 |v|), which is asserted, and this gate rejects it at 64 times its bound.
 (4) passes the output gate in bf16 (0.70) and fails it in fp16.
 
-Measured on an MI355X, worst err / bound over all cases and families of this file:
-  causal forward  bf16 0.59   fp16 0.51
-  GQA forward     bf16 0.60   fp16 0.54
-  decode          bf16 0.50   fp16 0.49
-  paged decode    bf16 0.50   fp16 0.47   (bitwise the contiguous decode)
+Two more are planted for the kernels test_weight_readout_fwd.py reads (full attention, flat
+inputs): (5) a stale K tile at a chain seam -- the first 64 keys of head 1's first query tile
+scored against head 0's K -- in all 128 rows of the tile and in row 5 alone: the readout rejects
+both at thousands of times its bound (2e3 bf16, 1.5e4 fp16 for the single row); the output gate,
+printed, rejects both too in either type (another head's weights are wrong by the whole weight,
+not by one key's).  (6) In a ragged batch of 65 and 257 keys the last key of the longer sequence
+dropped in its last row alone: rejected at 64 (bf16) / 510 (fp16) times the bound; the output
+gate, printed and not asserted, rejects it in both types as well (one key of 257 is 4e-3 of v).
+
+The many-head cases (chain_cases: the chained persistent kernels need a query tile per workgroup
+of a two-per-compute-unit grid, so hundreds of heads share a seed) take q ~ 2.5 N(0, 1) for
+steep: with 3 N(0, 1) the largest row span over so many rows is 43 to 46 log2 units, past the
+cap.  Asserted for their seeds at 256 compute units: no row spans more than 40 log2 units
+(measured 33.6 to 36.1) and the row maximum moves between 64-key tiles in at least a third of the
+rows; the per-head spread is not bounded there (measured minimum 19.5 natural units).
+
+Split-KV partial formats (attention_v2; split_extra, emulate_v2).  fp32 partials pass the bound
+as it stands.  A 16-bit partial is one more rounding of x = P / f, f the split's share of the
+row, which the combine scales back by f.  Scaled fp16 (x * 2^-e, 2^e <= 2 max x over the row's
+partial, with a selector V the probed window inside the split): a relative half-ulp 2^-11 above
+2^-14 (inside K), half the subnormal spacing below it, 2^-25 * 2^e <= 2^-24 max x, so the bound
+is K eps P + FLOOR + c * 2^-24 * max(P over window and split), c = 2 (the worst case doubled, as K
+doubles its two half-ulps).  The input type unscaled: K eps P + FLOOR + eps P (+ 2^-25, fp16
+subnormals).  test_split_kv_emulation_stays_inside_the_bound holds emulate_v2 (per-split
+normalised partial, the rounding to the format, {lse, e}, the base-2 combine) to 0.75 of these.
+
+Measured on an MI355X, worst err / bound over all cases and families (emulation beside it):
+                              bf16          fp16
+  causal forward              0.59 (0.50)   0.51 (0.50)
+  GQA forward                 0.60          0.54
+  decode                      0.50 (0.50)   0.49 (0.47)
+  paged decode                0.50          0.47          (bitwise the contiguous decode)
+  full forward                0.56 (0.50)   0.52 (0.49)   (the strided forms: 0.56, 0.50)
+  chain <final>, <final, gqa> 0.60          0.56
+  split-KV one-shot  fp32     0.59 (0.51)   0.54 (0.48)
+                     input    0.61 (0.57)   0.57 (0.54)
+                     scaled   0.59 (0.50)   0.71 (0.67)
+  split-KV arrive-first       0.50 / 0.57 / 0.51   0.45 / 0.53 / 0.66   (fp32 / input / scaled)
+  split-KV <fused walk>       0.58 / 0.60 / 0.58   0.52 / 0.58 / 0.72   (scaled: the walk; the others one-shot)
+  varlen                      0.58          0.54
 No kernel left the bound; the decode figures at Lk = 1041 are those of the emulation to three
 digits.
 """
@@ -129,6 +164,44 @@ def fwd_inputs(family, B, H, Hkv, L_, d, dtype):
     if family == "tempt":  # key j is aligned with row j - 1 of the group's first head
         k[:, :, 1:] = 1.5 * q[:, ::H // Hkv, :-1].float()
     return q, k.to(dtype)
+
+
+MANY_HEAD_STEEP = 2.5  # q scale of `steep` where hundreds of heads share a seed (see the docstring)
+MI355X_CUS = 256       # the CPU tests size the chain cases for this device; the GPU tests ask the device
+
+
+def chain_cases(cus):
+    """{name: (H, H_kv, L)} at B = 1, d = 128, of the chained persistent kernels' readout on a
+    device of `cus` compute units (grid = 2 * cus // 8 * 8 workgroups, fa_fwd.hip's launch rule):
+    one-item: a query tile per workgroup; uneven: some workgroups run two items and the item count
+    is no multiple of 8; cross-head: three query tiles per head, six key tiles per item, lists that
+    cross head boundaries; gqa: the uneven case with G = 4; walk / walk-uneven: attention_v2's
+    chained walk over two 256-key blocks, four query tiles per head."""
+    grid = 2 * cus // 8 * 8
+    uneven = grid // 2 + grid // 8 + 3
+    return {"one-item": (grid // 2, grid // 2, 256), "uneven": (uneven, uneven, 256),
+            "cross-head": (-(-grid // 3) + 5,) * 2 + (384,), "gqa": (-(-uneven // 4) * 4, -(-uneven // 4), 256),
+            "walk": (grid // 4, grid // 4, 512), "walk-uneven": (grid // 4 + 3, grid // 4 + 3, 512)}
+
+
+@functools.lru_cache(maxsize=None)
+def many_head_inputs(family, H, Hkv, L_, d, dtype):
+    """Storage-rounded q [1, H, L, d], k [1, H_kv, L, d] of a many-head case (flat / steep)."""
+    g = _gen("many", family, H, Hkv, L_, d)
+    q = torch.randn(1, H, L_, d, generator=g) * {"flat": 1.0, "steep": MANY_HEAD_STEEP}[family]
+    k = torch.randn(1, Hkv, L_, d, generator=g)
+    return q.to(dtype), k.to(dtype)
+
+
+def head_chunks(q, k, step=32):
+    """(h0, h1, q[:, h0:h1], k of those heads' K/V heads) in chunks of at most `step` query heads
+    (a multiple of the group size), so that no fp64 [heads, L, L] array grows past ~100 MB."""
+    H, Hkv = q.shape[1], k.shape[1]
+    G = H // Hkv
+    step = max(step // G, 1) * G
+    for h0 in range(0, H, step):
+        h1 = min(h0 + step, H)
+        yield h0, h1, q[:, h0:h1], k[:, h0 // G:-(-h1 // G)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -223,24 +296,27 @@ def _pad_keys(x, n):
     return np.concatenate([x, np.zeros(x.shape[:-1] + (n - x.shape[-1],), x.dtype)], axis=-1)
 
 
-def readout_check(got, P, vis, dtype):
+def readout_check(got, P, vis, dtype, extra=None):
     """(masked elements that are not +-0, non-finite elements, worst err / bound over the visible
-    ones) of a readout `got` [..., n >= Lk] (host, storage type) against fp64 weights P [..., Lk]."""
+    ones) of a readout `got` [..., n >= Lk] (host, storage type) against fp64 weights P [..., Lk].
+    extra [..., Lk]: a derived term added to the bound K eps P + FLOOR (the 16-bit split-KV
+    partial formats, split_extra); None: the bound as it stands."""
     n = got.shape[-1]
     P, vis = _pad_keys(P, n), _pad_keys(np.ascontiguousarray(vis), n)
+    extra = 0.0 if extra is None else _pad_keys(np.ascontiguousarray(extra, np.float64), n)
     bits = got.contiguous().view(torch.int16).numpy()
     x = got.double().numpy()
     assert x.shape == P.shape, (x.shape, P.shape)
     leaked = int(((bits & 0x7FFF) != 0)[~vis].sum())
     bad = int((~np.isfinite(x)).sum())
     with np.errstate(invalid="ignore"):
-        ratio = (np.abs(x - P) / (K_ULP * GATE[dtype][2] * P + FLOOR[dtype]))[vis]
+        ratio = (np.abs(x - P) / (K_ULP * GATE[dtype][2] * P + FLOOR[dtype] + extra))[vis]
     worst = float(np.where(np.isfinite(ratio), ratio, np.inf).max()) if ratio.size else 0.0
     return leaked, bad, worst
 
 
-def readout_gate(got, P, vis, dtype, label, limit=1.0, quiet=False):
-    leaked, bad, worst = readout_check(got, P, vis, dtype)
+def readout_gate(got, P, vis, dtype, label, limit=1.0, quiet=False, extra=None):
+    leaked, bad, worst = readout_check(got, P, vis, dtype, extra)
     if not quiet:
         print(f"readout {label}: worst err/bound={worst:.3f}")
     assert leaked == 0, (label, f"{leaked} masked or out-of-range keys read nonzero")
@@ -312,6 +388,71 @@ def emulate_forward(s2, dtype, smax=None):
     for t0 in range(0, s2.shape[1], TILE):
         st.fold(s2, slice(t0, min(t0 + TILE, s2.shape[1])), dtype, smax)
     w = st.normalised()
+    return w, torch.from_numpy(w).to(dtype)
+
+
+SCALED_C = 2
+PARTIAL_FORMATS = ("fp32", "input", "scaled")  # torch.float32, the input dtype, ops.PARTIAL_FP16_SCALED
+
+
+def _segments(Lk, d, kps):
+    """Starts of the key segments (probed window) x (key split): both edge sets."""
+    return np.array(sorted(set(range(0, Lk, d)) | set(range(0, Lk, kps))))
+
+
+def split_extra(P, d, kps, fmt, dtype):
+    """What a 16-bit split-KV partial format adds to K eps P + FLOOR, from the format alone.  A
+    split's normalised partial row is x = P / f (f the split's share of the row) over the keys of
+    the probed window inside the split, and the combine scales its error back by f.
+    scaled: x * 2^-e is stored as fp16 with 2^e <= 2 max(x): above 2^-14 a relative half-ulp 2^-11
+      (fp16 inputs: one of K's two spare eps; bf16: an eighth of one), below it half the subnormal
+      spacing, an absolute 2^-25 * 2^e <= 2^-24 max(x), reached when max(x) sits just above a power
+      of two: c * 2^-24 * max(P over window and split) with c = SCALED_C = 2, the worst case
+      doubled as K doubles the two half-ulps it is derived from (so that the emulation, which
+      meets the worst case at the smallest weights, stays at half the bound as it does there).
+    input: x stored as bf16 / fp16: one more half-ulp, eps P, and for fp16 the subnormal 2^-25.
+    fp32: nothing (None)."""
+    if fmt == "fp32":
+        return None
+    if fmt == "input":
+        return GATE[dtype][2] * P + (2.0 ** -25 if dtype == torch.float16 else 0.0)
+    seg = _segments(P.shape[-1], d, kps)
+    mx = np.maximum.reduceat(P, seg, axis=-1)
+    return SCALED_C * 2.0 ** -24 * np.repeat(mx, np.diff(np.append(seg, P.shape[-1])), axis=-1)
+
+
+def emulate_v2(s2, d, kps, fmt, dtype):
+    """attention_v2 on one query tile's rows, s2 [R, Lk] base-2 scores: per split of kps keys the
+    forward's 64-key tiles (P rounded, l from the rounded P), the normalised partial rounded to
+    the partial format -- scaled: per probed window of d keys (what one call's partial row holds)
+    times 2^-e, e the exponent of the row's largest value, to fp16 -- its {lse, e}, and the
+    base-2 combine in split order.  Returns (weights fp32, output storage tensor)."""
+    R, Lk = s2.shape
+    parts, lses = [], []
+    for k0 in range(0, Lk, kps):
+        st = _State(R, Lk)
+        for t0 in range(k0, min(k0 + kps, Lk), TILE):
+            st.fold(s2, slice(t0, min(t0 + TILE, k0 + kps, Lk)), dtype)
+        part = st.normalised()
+        if fmt == "input":
+            part = _round_to(part, dtype)
+        elif fmt == "scaled":
+            for w0 in range(0, Lk, d):
+                cols = slice(max(w0, k0), min(w0 + d, k0 + kps, Lk))
+                if cols.start >= cols.stop:
+                    continue
+                e = np.frexp(part[:, cols].max(axis=1))[1][:, None]  # max * 2^-e in [0.5, 1); 0 -> e = 0
+                part[:, cols] = np.ldexp(_round_to(np.ldexp(part[:, cols], -e), torch.float16), e)
+        parts.append(part)
+        with np.errstate(divide="ignore"):
+            lses.append(np.where(st.l > 0, st.m + np.log2(st.l), -np.inf).astype(np.float32))
+    M = np.max(lses, axis=0)
+    acc, wsum = np.zeros((R, Lk), np.float32), np.zeros(R, np.float32)
+    for part, lse in zip(parts, lses):
+        wgt = _exp2_diff(lse, M)
+        acc += wgt[:, None] * part
+        wsum += wgt
+    w = acc * (np.float32(1) / wsum)[:, None]
     return w, torch.from_numpy(w).to(dtype)
 
 
@@ -491,6 +632,22 @@ def test_input_families_have_their_properties():
                         checked += 1
                 assert checked > 0 or (lens is None and not causal), label
     assert all(v >= 20 for v in reached.values()), reached
+    # the many-head cases (q ~ MANY_HEAD_STEEP N(0, 1)), sized for an MI355X, in head chunks: the
+    # row cap and the moving maximum; the per-head spread is printed, not bounded
+    least = {}
+    for (name, (H, Hkv, L_)), dtype in itertools.product(chain_cases(MI355X_CUS).items(), DTYPES):
+        span, moved, rows, spread = 0.0, 0, 0, np.inf
+        for _, _, qc, kc in head_chunks(*many_head_inputs("steep", H, Hkv, L_, 128, dtype)):
+            s = _scores(qc, kc)
+            assert np.isfinite(s).all() and np.abs(s).max() < 1e3, (name, IDS[dtype])
+            span = max(span, float((s.max(-1) - s.min(-1)).max()) * LOG2E)
+            mv = _moving_max_rows(s, np.ones(s.shape, bool))
+            moved, rows = moved + int(mv.sum()), rows + mv.size
+            spread = min(spread, float((s.max(axis=(-1, -2)) - s.min(axis=(-1, -2))).min()))
+        assert span <= 40, (name, IDS[dtype], span)
+        assert moved >= rows / 3, (name, IDS[dtype], moved, rows)
+        least[name, IDS[dtype]] = (round(span, 1), round(spread, 1))
+    print("many-head steep (largest row span in log2 units, least per-head spread in natural units):", least)
 
 
 EMU_FWD = (1, 2, 64, 384)  # B, H, d, L: six query tiles' worth of rows, six key tiles
@@ -555,6 +712,30 @@ def test_emulation_stays_inside_the_bound(family, dtype):
     print({k_: round(v, 3) for k_, v in worst.items()})
 
 
+EMU_V2 = ((2, 64, 512, 64), (2, 64, 512, 256), (1, 128, 1000, 64), (1, 128, 1000, 256))  # H, d, L, keys per split
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=IDS.get)
+@pytest.mark.parametrize("family", FAMILIES[:2])
+def test_split_kv_emulation_stays_inside_the_bound(family, dtype):
+    """The full (non-causal) forward, and attention_v2's steps per partial format: at most 0.75 of
+    K eps P + FLOOR + split_extra -- fp32 partials under the bound as it stands."""
+    worst = {}
+    for H, d, L_, kps in EMU_V2:
+        q, k = fwd_inputs(family, 1, H, H, L_, d, dtype)
+        P, vis, s = fwd_weights(q, k, False)
+        s2 = _base2(s, vis, d).reshape(H * L_, L_)
+        if kps == 64:
+            out = emulate_forward(s2, dtype)[1].reshape(P.shape)
+            worst[f"full d{d} L{L_}"] = readout_gate(out, P, vis, dtype, "emulation full", limit=0.75, quiet=True)
+        for fmt in PARTIAL_FORMATS:
+            out = emulate_v2(s2, d, kps, fmt, dtype)[1].reshape(P.shape)
+            r = readout_gate(out, P, vis, dtype, f"emulation v2 {fmt} d{d} L{L_} kps{kps}", limit=0.75, quiet=True,
+                             extra=split_extra(P, d, kps, fmt, dtype))
+            worst[fmt] = max(worst.get(fmt, 0.0), r)
+    print(f"emulation {family} {IDS[dtype]}:", {k_: round(v, 3) for k_, v in worst.items()})
+
+
 def _output_gate_accepts(w, P, dtype, seed):
     """The parity tests' gate (A + eps |ref|, mean_rel) on O = weights @ V, V ~ N(0, 1)."""
     d = 64
@@ -613,6 +794,38 @@ def test_readout_gate_rejects_what_the_output_gate_accepts(dtype):
     r, why = rejected(P, vis, out)
     assert r, why
     print("premax: readout", why, "output gate accepts:", _output_gate_accepts(w, P, dtype, 1))
+
+    # 5. a stale K tile at a chain seam: the first 64 keys of head 1's first query tile scored
+    # against head 0's K (full forward, two heads); in every row of the tile, then in row 5 alone
+    B, H, d, L_ = EMU_FWD
+    q, k = fwd_inputs("flat", B, H, H, L_, d, dtype)
+    P, vis, s = fwd_weights(q, k, False)
+    stale = q[0, 1].double().numpy() @ k[0, 0, :TILE].double().numpy().T / np.sqrt(d)
+    for rows in (slice(0, 128), slice(5, 6)):
+        sb = s.copy()
+        sb[0, 1, rows, :TILE] = stale[rows]
+        w, out = emulate_forward(_base2(sb, vis, d).reshape(B * H * L_, L_), dtype)
+        w, out = w.reshape(s.shape), out.reshape(s.shape)
+        r, why = rejected(P, vis, out)
+        assert r, (rows, why)
+        print(f"stale K tile, rows {rows.start}..{rows.stop - 1}: readout", why, "output gate accepts:",
+              _output_gate_accepts(w, P, dtype, 3))
+
+    # 6. a ragged batch of 65 and 257 keys (full attention inside each sequence): the last key of
+    # the longer sequence dropped in its last row alone
+    for n, drop in ((65, False), (257, False), (257, True)):
+        q, k = fwd_inputs("flat", 1, 1, 1, n, 64, dtype)
+        P, vis, s = fwd_weights(q, k, False)
+        kvis = np.array(vis)
+        if drop:
+            kvis[..., n - 1, n - 1] = False
+        w, out = emulate_forward(_base2(s, kvis, 64).reshape(n, n), dtype)
+        w, out = w.reshape(s.shape), out.reshape(s.shape)
+        r, why = rejected(P, vis, out)
+        assert r == drop, (n, drop, why)
+        if drop:  # (the output gate's verdict is printed, not asserted)
+            print("dropped last key of the 257-key sequence, row 256: readout", why, "output gate accepts:",
+                  _output_gate_accepts(w, P, dtype, 4))
 
 
 # ----------------------------------------------------------------------------------------
