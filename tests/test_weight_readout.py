@@ -102,8 +102,31 @@ Measured on an MI355X, worst err / bound over all cases and families (emulation 
   split-KV arrive-first       0.50 / 0.57 / 0.51   0.45 / 0.53 / 0.66   (fp32 / input / scaled)
   split-KV <fused walk>       0.58 / 0.60 / 0.58   0.52 / 0.58 / 0.72   (scaled: the walk; the others one-shot)
   varlen                      0.58          0.54
+  d-tiled d = 384             0.50 (0.50)   0.48 (0.48)   (padded d = 300: 0.50)
+  d-tiled d = 512 <paired>    0.51 (0.51)   0.51 (0.51)   (padded d = 400: 0.49)
+  raw partial        fp32     0.43 (0.42)   0.43 (0.39)   (against the shard-local weights; the
+                     input    0.52 (0.53)   0.52 (0.48)    strided q forms included; bounds:
+                     scaled   0.48 (0.48)   0.69 (0.64)    test_weight_readout_partial.py)
+  partial lse                 0.13 (0.08)   0.13 (0.09)   (every format alike)
+  combine            fp32     0.50 (0.49)   0.48 (0.47)
+                     input    0.56 (0.54)   0.56 (0.54)
+                     scaled   0.52 (0.50)   0.70 (0.67)
 No kernel left the bound; the decode figures at Lk = 1041 are those of the emulation to three
-digits.
+digits.  (The emulations of the last nine rows run on fewer cases than the kernels: L = 130 and
+600 of the d-tiled lengths, the first and the last of the partial cases.)
+
+Four more defects are planted for the kernels test_weight_readout_dtiled.py and
+test_weight_readout_partial.py read, each rejected by this gate; the output gate's verdict is
+printed and rejects them too at these shapes (a few hundred keys at most: one weight is not small
+there).  d-tiled wave pairs (d = 512, L = 600, emulate_dtiled_pair): (7) on the tile where a row
+of wave 1 rose most (2^7.8, steep) wave 0 misses its partner's alpha, in every row of the wave and
+in that row alone: the keys of the earlier tiles in wave 0's half of the columns are overweighted,
+1.5e4 (bf16) / 1.1e5 (fp16) times the bound; (8) the partner's row sum taken from the wave's own
+row of the same index (flat): 68 / 530 times the bound.  Partial and combine (flat, d = 64, Lk =
+193 in shards of 64 keys, emulate_partial_combine): (9) the last key of the last shard, a shard
+of that one key, dropped in the last row of each chunk: the raw partial reads 0 for a weight of
+1, 64 to 85 (bf16) / 510 to 680 (fp16) times its bound, the combined row 51 to 64 / 410 to 510;
+(10) the combine decoding row r's scaled partial with the exponent of row r ^ 1: 450 / 3600.
 """
 import functools
 import itertools
@@ -296,27 +319,32 @@ def _pad_keys(x, n):
     return np.concatenate([x, np.zeros(x.shape[:-1] + (n - x.shape[-1],), x.dtype)], axis=-1)
 
 
-def readout_check(got, P, vis, dtype, extra=None):
+def readout_check(got, P, vis, dtype, extra=None, k_ulp=K_ULP):
     """(masked elements that are not +-0, non-finite elements, worst err / bound over the visible
-    ones) of a readout `got` [..., n >= Lk] (host, storage type) against fp64 weights P [..., Lk].
-    extra [..., Lk]: a derived term added to the bound K eps P + FLOOR (the 16-bit split-KV
-    partial formats, split_extra); None: the bound as it stands."""
+    ones) of a readout `got` [..., n >= Lk] (host; the storage type, or float32: a decoded fp32 or
+    scaled split-KV partial, its +-0 test on the float32 bit pattern) against fp64 weights P
+    [..., Lk].  extra [..., Lk]: a derived term added to the bound K eps P + FLOOR (the 16-bit
+    split-KV partial formats, split_extra); None: the bound as it stands.  k_ulp: K (K_ULP - 1
+    for a partial stored without the output's rounding, test_weight_readout_partial.py)."""
     n = got.shape[-1]
     P, vis = _pad_keys(P, n), _pad_keys(np.ascontiguousarray(vis), n)
     extra = 0.0 if extra is None else _pad_keys(np.ascontiguousarray(extra, np.float64), n)
-    bits = got.contiguous().view(torch.int16).numpy()
+    if got.dtype == torch.float32:
+        nonzero = (got.contiguous().view(torch.int32).numpy() & 0x7FFFFFFF) != 0
+    else:
+        nonzero = (got.contiguous().view(torch.int16).numpy() & 0x7FFF) != 0
     x = got.double().numpy()
     assert x.shape == P.shape, (x.shape, P.shape)
-    leaked = int(((bits & 0x7FFF) != 0)[~vis].sum())
+    leaked = int(nonzero[~vis].sum())
     bad = int((~np.isfinite(x)).sum())
     with np.errstate(invalid="ignore"):
-        ratio = (np.abs(x - P) / (K_ULP * GATE[dtype][2] * P + FLOOR[dtype] + extra))[vis]
+        ratio = (np.abs(x - P) / (k_ulp * GATE[dtype][2] * P + FLOOR[dtype] + extra))[vis]
     worst = float(np.where(np.isfinite(ratio), ratio, np.inf).max()) if ratio.size else 0.0
     return leaked, bad, worst
 
 
-def readout_gate(got, P, vis, dtype, label, limit=1.0, quiet=False, extra=None):
-    leaked, bad, worst = readout_check(got, P, vis, dtype, extra)
+def readout_gate(got, P, vis, dtype, label, limit=1.0, quiet=False, extra=None, k_ulp=K_ULP):
+    leaked, bad, worst = readout_check(got, P, vis, dtype, extra, k_ulp)
     if not quiet:
         print(f"readout {label}: worst err/bound={worst:.3f}")
     assert leaked == 0, (label, f"{leaked} masked or out-of-range keys read nonzero")
