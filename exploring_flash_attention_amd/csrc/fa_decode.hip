@@ -34,6 +34,7 @@
 // base from one scalar table read per tile, the entry clamped to [0, num_blocks - 1] first.  The
 // tiles, their order and the arithmetic are those of the contiguous kernels (bitwise the same
 // result on the gathered cache), whose code is not touched: everything paged is if constexpr.
+#include <atomic>
 #include <type_traits>
 
 #include "fa_decode.hpp"
@@ -457,10 +458,22 @@ static hipError_t launch_decode_one(const DecodeArgs& a, hipStream_t s) {
         {"fa_decode_kernel<16 rows>", "fa_decode_kernel<32 rows>", "fa_decode_kernel<64 rows>"},
         {"fa_decode_kernel<16 rows, paged>", "fa_decode_kernel<32 rows, paged>", "fa_decode_kernel<64 rows, paged>"}};
     constexpr int lds = decode_lds_bytes(D);
-    // (more than 64 KiB of dynamic LDS at d = 128: raise the kernel's limit once)
-    static const hipError_t attr = hipFuncSetAttribute((const void*)fa_decode_kernel<T, D, NQB, PAGED>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) (void)hipGetLastError();
+    // (more than 64 KiB of dynamic LDS at d = 128: raise the kernel's limit once per device.  The
+    // attribute is set on the device that is current at the call -- the stream's, by the header's
+    // contract -- so that is the device remembered; one that cannot be told is set on every launch)
+    static std::atomic<unsigned long long> raised{0};
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        (void)hipGetLastError();
+        dev = -1;
+    }
+    if (dev < 0 || !(raised.load(std::memory_order_relaxed) >> dev & 1)) {
+        if (hipFuncSetAttribute((const void*)fa_decode_kernel<T, D, NQB, PAGED>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+            (void)hipGetLastError();
+        else if (dev >= 0)
+            raised.fetch_or(1ull << dev, std::memory_order_relaxed);
+    }
     const int64_t grid = (int64_t)a.B * a.Hkv * a.nsplit;
     note_kernel(names[PAGED][NQB == 1 ? 0 : NQB == 2 ? 1 : 2], grid);
     hipLaunchKernelGGL((fa_decode_kernel<T, D, NQB, PAGED>), dim3((unsigned)grid), dim3(kDecThreads), lds, s, a);

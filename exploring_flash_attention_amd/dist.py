@@ -268,8 +268,11 @@ def splitkv_attention_native(q, k_shard, v_shard, comm, gather=False, partial_dt
     if workspace is None:
         workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=q.device)
     out = torch.empty((B, H, L if gather else L // W, d), dtype=q.dtype, device=q.device)
-    _dcheck(dist_lib().fa_fwd_v2_dist(ops._ptr(q), ops._ptr(k_shard), ops._ptr(v_shard), ops._ptr(out),
-                                      B, H, L, d, comm.handle, int(bool(gather)), ops._ptr(workspace),
-                                      workspace.numel(), ops._DTYPES[q.dtype], ops._PDTYPES[pd],
-                                      ops._stream(q)))
+    # the tensors' device current for the launch (ops._on_tensor_device has the reason); the
+    # library refuses a communicator that was made on another device
+    with torch.cuda.device(q.device):
+        _dcheck(dist_lib().fa_fwd_v2_dist(ops._ptr(q), ops._ptr(k_shard), ops._ptr(v_shard), ops._ptr(out),
+                                          B, H, L, d, comm.handle, int(bool(gather)), ops._ptr(workspace),
+                                          workspace.numel(), ops._DTYPES[q.dtype], ops._PDTYPES[pd],
+                                          ops._stream(q)))
     return out

@@ -20,6 +20,7 @@ counterpart in the reference.
 """
 import contextlib
 import ctypes
+import functools
 import threading
 
 import torch
@@ -100,6 +101,24 @@ def _unpad_into(o_pad, o, d):
     if o_pad is not o:
         o.copy_(o_pad[..., :d])
     return o
+
+
+def _on_tensor_device(fn):
+    """Run a launching operator with the device of its first tensor current.  The stream handed
+    to the library is that device's current stream, but the default stream's handle is 0 on every
+    device and the runtime resolves it -- and the occupancy plans, the counter reset and torch's
+    temporaries -- to the CURRENT device: without the guard a call on cuda:1 tensors while cuda:0
+    is current would enqueue on cuda:0.  The caller's current device is restored on return."""
+    first = fn.__code__.co_varnames[0]
+
+    @functools.wraps(fn)
+    def guarded(*args, **kw):
+        t = args[0] if args else kw.get(first)
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            with torch.cuda.device(t.device):
+                return fn(*args, **kw)
+        return fn(*args, **kw)  # not a device tensor: the operator's own checks name it
+    return guarded
 
 
 def _stream(t):
@@ -233,6 +252,7 @@ def _attention_v1_gqa(q, k, v, o, causal):
     return _unpad_into(op, o, d)
 
 
+@_on_tensor_device
 def attention_v1(q, k, v, out=None, causal=False):
     """FA-v1 fused forward: O = softmax(q k^T / sqrt(d)) v.  Any 1 <= d <= 256 (head dims
     without a kernel are zero-padded to the next one, see kernel_head_dim).  q, k, v and out
@@ -290,6 +310,7 @@ def _varlen_strides(ts, d):
     return tuple((ctypes.c_int64 * 2)(*t.stride()[:2]) for t in ts)
 
 
+@_on_tensor_device
 def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
     """Variable-length (token-packed) self-attention, one launch for a ragged batch
     (fa_fwd_varlen): q ``[T, H, d]``, k and v ``[T, H_kv, d]``, bfloat16 or float16, H a multiple
@@ -382,6 +403,7 @@ def _d_tiles(d, d_tile_qk, d_tile_v):
             dflt if d_tile_v is None else int(d_tile_v))
 
 
+@_on_tensor_device
 def attention_tiled_d(q, k, v, d_tile_qk=None, d_tile_v=None, out=None):
     """FA-v1 d-tiled forward (O_acc in VGPRs); d tiles as in the reference launcher
     (0 < d_tile <= d; default min(32, d) up to d = 256, 128 above -- see _d_tiles).  d <= 256: one LDS tile holds a whole row and the
@@ -456,6 +478,7 @@ def v2_split_plan(B, H, L, d, kv_tiles_per_block=4, dtype=torch.bfloat16, blocks
     return kb.value, g.value, p.value
 
 
+@_on_tensor_device
 def attention_v2(q, k, v, kv_tiles_per_block=4, d_tile_qk=None, d_tile_v=None, partial_dtype=None,
                  out=None, workspace=None, blocks_per_workgroup=None, workspace_zeroed=False):
     """FA-v2 split-KV forward (partial kernel + combine kernel).
@@ -519,6 +542,7 @@ def attention_v2(q, k, v, kv_tiles_per_block=4, d_tile_qk=None, d_tile_v=None, p
     return _unpad_into(op, o, d)
 
 
+@_on_tensor_device
 def attention_partial(q, k, v, chunk_rows=None, partial_dtype=None, o_part=None, lse=None):
     """Split-KV partial over one whole key range (k, v: [B, H, Lk, d]).
 
@@ -559,6 +583,7 @@ def attention_partial(q, k, v, chunk_rows=None, partial_dtype=None, o_part=None,
     return o_part, lse
 
 
+@_on_tensor_device
 def combine(o_part, lse, B, H, dtype, out=None):
     """Combine ``S`` partials o_part ``[S, B*H, L, d]`` / lse ``[S, B*H, L]`` -> ``[B, H, L, d]``.
 
@@ -598,6 +623,7 @@ def decode_plan(B, H, H_kv, Lq, Lk, d, num_splits=None, dtype=torch.bfloat16, cu
     return splits.value, kps.value, nbytes.value
 
 
+@_on_tensor_device
 def attention_decode(q, k, v, seqlens_k=None, causal=True, num_splits=None, out=None, workspace=None):
     """KV-cache decode attention: q ``[B, H, Lq, d]`` (Lq small) against k, v ``[B, H_kv, Lk, d]``,
     bfloat16 or float16, H a multiple of H_kv (query head h reads K/V head h // (H // H_kv)) and
@@ -683,6 +709,7 @@ def attention_decode(q, k, v, seqlens_k=None, causal=True, num_splits=None, out=
 DECODE_PAGE_MULTIPLE = 64     # keys per page: a multiple of the decode kernel's key tile
 
 
+@_on_tensor_device
 def attention_decode_paged(q, k_cache, v_cache, block_table, seqlens_k=None, max_seqlen_k=None, causal=True,
                            num_splits=None, out=None, workspace=None):
     """attention_decode on a paged KV cache, read in place through a block table
