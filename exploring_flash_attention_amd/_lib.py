@@ -46,6 +46,8 @@ SIGNATURES = {
     "fa_fwd_v1_gqa": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, ctypes.c_double, ctypes.c_uint, _I, _P]),
     "fa_fwd_varlen": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double,
                            ctypes.c_uint, _I, _P]),
+    "fa_fwd_varlen_kv": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
+                              ctypes.c_double, ctypes.c_uint, _I, _P]),
     "fa_fwd_v1_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_tiled_d": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
     "fa_fwd_v1_tiled_d_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, ctypes.c_double, _I, _P]),

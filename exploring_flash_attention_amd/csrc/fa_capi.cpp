@@ -500,10 +500,13 @@ int fa_fwd_v1_gqa(const void* q, const void* k, const void* v, void* o, int64_t 
     return ok();
 }
 
-int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens, int64_t B,
-                  int64_t total_tokens, int64_t max_seqlen, int64_t H, int64_t H_kv, int64_t d,
-                  const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
-                  double softmax_scale, unsigned flags, int dtype, void* stream) {
+// fa_fwd_varlen (kv = false: one cu_seqlens for both sides, the *_k arguments unused) and
+// fa_fwd_varlen_kv (kv = true) share their checks
+static int fwd_varlen_impl(bool kv, const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens,
+                           const int32_t* cu_seqlens_k, const int32_t* seqused_k, int64_t B, int64_t total_tokens,
+                           int64_t total_tokens_k, int64_t max_seqlen, int64_t max_seqlen_k, int64_t H, int64_t H_kv,
+                           int64_t d, const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
+                           double softmax_scale, unsigned flags, int dtype, void* stream) {
     fa::Elem e;
     if (flags & ~FA_FWD_CAUSAL)
         return fail(FA_ERR_INVALID_ARG, "varlen: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", flags);
@@ -512,6 +515,10 @@ int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const in
         return fail(FA_ERR_INVALID_ARG, "varlen: total_tokens=%lld must not be negative", (long long)total_tokens);
     if (max_seqlen <= 0)
         return fail(FA_ERR_INVALID_ARG, "varlen: max_seqlen=%lld must be positive", (long long)max_seqlen);
+    if (kv && total_tokens_k < 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: total_tokens_k=%lld must not be negative", (long long)total_tokens_k);
+    if (kv && max_seqlen_k <= 0)
+        return fail(FA_ERR_INVALID_ARG, "varlen: max_seqlen_k=%lld must be positive", (long long)max_seqlen_k);
     if (H <= 0 || d <= 0)
         return fail(FA_ERR_INVALID_ARG, "varlen: H=%lld and d=%lld must be positive", (long long)H, (long long)d);
     if (H_kv <= 0 || H_kv > H || H % H_kv != 0)
@@ -526,9 +533,16 @@ int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const in
     if (int st = check_ptrs(q, k, v, o)) return st;
     if (!cu_seqlens || ((uintptr_t)cu_seqlens & 3))
         return fail(FA_ERR_INVALID_ARG, "varlen: cu_seqlens must be non-null and 4-byte aligned");
+    if (kv && (!cu_seqlens_k || ((uintptr_t)cu_seqlens_k & 3)))
+        return fail(FA_ERR_INVALID_ARG, "varlen: cu_seqlens_k must be non-null and 4-byte aligned");
+    if (kv && ((uintptr_t)seqused_k & 3))
+        return fail(FA_ERR_INVALID_ARG, "varlen: seqused_k must be null or 4-byte aligned");
     if (total_tokens > (int64_t)0x7fffffff)
         return fail(FA_ERR_UNSUPPORTED, "varlen: total_tokens=%lld exceeds 2^31-1 (cu_seqlens is int32)",
                     (long long)total_tokens);
+    if (kv && total_tokens_k > (int64_t)0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "varlen: total_tokens_k=%lld exceeds 2^31-1 (cu_seqlens_k is int32)",
+                    (long long)total_tokens_k);
     // (a length beyond the tokens is clamped on the device anyway: the grid need not cover it)
     const int64_t msl = max_seqlen < total_tokens ? max_seqlen : total_tokens;
     const int64_t nqt = (msl + fa::kBQ - 1) / fa::kBQ;
@@ -570,9 +584,37 @@ int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const in
     a.max_seqlen = (int)msl;
     a.total_rows = total_tokens;
     kernels_begin();
+    if (kv) {
+        // (a key range beyond the rows of k / v is clamped on the device, as the query side is)
+        a.cu_seqlens_k = cu_seqlens_k;
+        a.seqused_k = seqused_k;
+        a.max_seqlen_k = (int)(max_seqlen_k < total_tokens_k ? max_seqlen_k : total_tokens_k > 0 ? total_tokens_k : 1);
+        a.total_rows_k = total_tokens_k;
+        if (hipError_t he = fa::launch_fwd_varlen_kv(e, (int)d, (flags & FA_FWD_CAUSAL) != 0, a, (hipStream_t)stream))
+            return hip_fail(he, "fa_fwd_varlen_kv launch");
+        return ok();
+    }
     if (hipError_t he = fa::launch_fwd_varlen(e, (int)d, (flags & FA_FWD_CAUSAL) != 0, a, (hipStream_t)stream))
         return hip_fail(he, "fa_fwd_varlen launch");
     return ok();
+}
+
+int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens, int64_t B,
+                  int64_t total_tokens, int64_t max_seqlen, int64_t H, int64_t H_kv, int64_t d,
+                  const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
+                  double softmax_scale, unsigned flags, int dtype, void* stream) {
+    return fwd_varlen_impl(false, q, k, v, o, cu_seqlens, nullptr, nullptr, B, total_tokens, 0, max_seqlen, 0, H, H_kv,
+                           d, q_strides, kv_strides, o_strides, softmax_scale, flags, dtype, stream);
+}
+
+int fa_fwd_varlen_kv(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens,
+                     const int32_t* cu_seqlens_k, const int32_t* seqused_k, int64_t B, int64_t total_tokens,
+                     int64_t total_tokens_k, int64_t max_seqlen, int64_t max_seqlen_k, int64_t H, int64_t H_kv,
+                     int64_t d, const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
+                     double softmax_scale, unsigned flags, int dtype, void* stream) {
+    return fwd_varlen_impl(true, q, k, v, o, cu_seqlens, cu_seqlens_k, seqused_k, B, total_tokens, total_tokens_k,
+                           max_seqlen, max_seqlen_k, H, H_kv, d, q_strides, kv_strides, o_strides, softmax_scale,
+                           flags, dtype, stream);
 }
 
 int fa_fwd_v1_tiled_d(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,

@@ -1,7 +1,8 @@
 // fa_fwd_kernel.hpp -- flash-attention forward kernel for MI355X (gfx950 / CDNA4), included by
 // fa_fwd.hip (contiguous [B,H,L,d] launches), fa_fwd_strided.hip (strided launches),
-// fa_fwd_causal.hip (the causal instantiations), fa_fwd_gqa.hip (grouped-query) and
-// fa_fwd_varlen.hip (token-packed ragged batches).
+// fa_fwd_causal.hip (the causal instantiations), fa_fwd_gqa.hip (grouped-query),
+// fa_fwd_varlen.hip (token-packed ragged batches) and fa_fwd_varlen_kv.hip (the same with key
+// lengths of their own).
 //
 // One kernel template serves the three reference kernel families:
 //   final mode   (MODE=kFinal): FA-v1 fused / d-tiled forward
@@ -113,12 +114,19 @@ namespace fa {
 // length come from a.cu_seqlens on the device, clamped so that no descriptor and no store can
 // leave rows [0, T), and stand in for a.Lq / a.Lk.  An item whose tile starts past the length
 // returns before any barrier or DMA.  MHA runs with kv_group = 1.
+// KVLEN (VARLEN only; instantiated in fa_fwd_varlen_kv.hip): the keys of sequence b are rows of k / v
+// named by a second array, a.cu_seqlens_k (cut to a.seqused_k[b] rows if given), clamped against
+// a.total_rows_k and a.max_seqlen_k as the query side is against T and max_seqlen.  Lk != Lq: the
+// causal diagonal is aligned bottom-right, query row i sees keys j <= i + s, s = Lk - Lq, so the
+// first tile that crosses the diagonal is no multiple of kBQ / kBK any more; a row may see no key
+// at all (s < 0, or Lk = 0) and is then written as zeros.
 template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false,
-          bool GQA = false, bool VARLEN = false>
+          bool GQA = false, bool VARLEN = false, bool KVLEN = false>
 __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void fa_fwd_kernel(FwdArgs a) {
     static_assert(!CAUSAL || (MODE == kFinal && (!STRIDED || VARLEN)), "causal: final mode, contiguous tensors");
     static_assert(!GQA || (MODE == kFinal && (!STRIDED || VARLEN)), "GQA: final mode, contiguous tensors");
     static_assert(!VARLEN || (MODE == kFinal && TAIL && STRIDED && GQA), "varlen: final mode, runtime lengths, strided rows");
+    static_assert(!KVLEN || VARLEN, "separate key lengths: a varlen variant");
     using M = Mma<T>;
     using v8 = typename M::v8;
     constexpr int RB = kRB;                   // 32-row query blocks per wave
@@ -174,7 +182,29 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         // no row of this tile exists (a short or empty sequence): uniform exit, nothing touched
         if ((int64_t)qt * kBQ >= vl_len) return;
     }
-    const int64_t Lq = VARLEN ? vl_len : a.Lq, Lk = VARLEN ? vl_len : a.Lk;
+    // KVLEN: keys [start_k, start_k + len_k) of k / v, clamped like the query side (64-bit, then
+    // uniform): start_k = clamp(cu_k[b], 0, Tk), len_k = clamp(cu_k[b+1] - start_k, 0, min(max_seqlen_k,
+    // Tk - start_k)), then at most clamp(seqused_k[b], 0, ..) -- start_k + len_k <= Tk whatever the
+    // arrays hold, and every K / V descriptor below covers rows of [start_k, start_k + len_k) only.
+    int vk_start = 0, vk_len = 0;
+    if constexpr (KVLEN) {
+        const unsigned b = (unsigned)bh / (unsigned)a.H;
+        const int64_t nt = a.total_rows_k;  // Tk
+        const int64_t c0 = a.cu_seqlens_k[b], c1 = a.cu_seqlens_k[b + 1];
+        const int64_t st = c0 < 0 ? 0 : c0 > nt ? nt : c0;
+        const int64_t room = nt - st < a.max_seqlen_k ? nt - st : a.max_seqlen_k;
+        int64_t n = c1 - st;
+        n = n < 0 ? 0 : n > room ? room : n;
+        if (a.seqused_k) {
+            const int64_t u = a.seqused_k[b];
+            n = u < 0 ? 0 : u < n ? u : n;
+        }
+        vk_start = __builtin_amdgcn_readfirstlane((int)st);
+        vk_len = __builtin_amdgcn_readfirstlane((int)n);
+    }
+    const int64_t Lq = VARLEN ? vl_len : a.Lq, Lk = KVLEN ? vk_len : VARLEN ? vl_len : a.Lk;
+    // KVLEN: the offset of the causal diagonal, query row i sees keys j <= i + kv_s
+    const int64_t kv_s = KVLEN ? Lk - Lq : 0;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -193,7 +223,10 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int64_t kv_begin = (int64_t)split * a.kv_per_split;
     // (causal: the keys up to the query tile's last row -- a multiple of the KV tile unless it
     // is Lk itself, where the partial-last-tile path applies as ever)
-    const int64_t kv_end = CAUSAL ? ((int64_t)(qt + 1) * kBQ < Lk ? (int64_t)(qt + 1) * kBQ : Lk)
+    // (KVLEN: up to the diagonal of the tile's last row, clamp(s + kBQ (qt + 1), 0, Lk))
+    const int64_t kv_diag = kv_s + (int64_t)(qt + 1) * kBQ;
+    const int64_t kv_end = KVLEN && CAUSAL ? (kv_diag < 0 ? 0 : kv_diag < Lk ? kv_diag : Lk)
+                           : CAUSAL ? ((int64_t)(qt + 1) * kBQ < Lk ? (int64_t)(qt + 1) * kBQ : Lk)
                            : VARLEN ? Lk
                            : kv_begin + a.kv_per_split < Lk ? kv_begin + a.kv_per_split : Lk;
     const int nkv = (int)(kv_end - kv_begin);
@@ -207,7 +240,7 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     const int64_t q_head = VARLEN    ? vl_start * a.q_stride[2] + hh * a.q_stride[1]
                            : STRIDED ? hb * a.q_stride[0] + hh * a.q_stride[1]
                                      : bh * a.Lq * D;
-    int64_t k_head = VARLEN    ? vl_start * a.k_stride[2] + (int64_t)((unsigned)vl_head / (unsigned)a.kv_group) * a.k_stride[1]
+    int64_t k_head = VARLEN    ? (KVLEN ? vk_start : vl_start) * a.k_stride[2] + (int64_t)((unsigned)vl_head / (unsigned)a.kv_group) * a.k_stride[1]
                      : STRIDED ? hb * a.k_stride[0] + hh * a.k_stride[1]
                                : bh * a.Lk * D;
     if constexpr (GQA && !VARLEN) k_head = gqa_kv_head(a, bh) * a.Lk * D;
@@ -226,6 +259,24 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     // Q^T fragments (B operand): lane holds Q[row][16*ks + 8*hf + 0..7] of each of its
     // RB row blocks.  Rows past Lq read zeros and are never stored.
     const int64_t q_row0 = q_tile0 + wid * kRowsPerWave + l32;
+    if constexpr (KVLEN) {
+        // no key for any row of this tile (Lk = 0, or causal with the whole tile above the
+        // diagonal): its rows are zeros.  Uniform exit, before any DMA or barrier.
+        if (nkv <= 0) {
+            unsigned short* const Oz = (unsigned short*)a.o + vl_start * a.o_stride[2] + hh * a.o_stride[1];
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const int64_t q_row = q_row0 + 32 * r;
+                if (q_row >= Lq) continue;
+#pragma unroll
+                for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                    for (int gp = 0; gp < 4; gp += 2)
+                        *(u32x4*)(Oz + q_row * a.o_stride[2] + db * 32 + 8 * gp + 8 * hf) = u32x4{0u, 0u, 0u, 0u};
+            }
+            return;
+        }
+    }
     v8 qf[RB][NKS];
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
@@ -409,12 +460,18 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     // is folded into the same bound).  A tile may be wholly masked for a wave (wave 0 against
     // keys 64.. of its own query tile): its row max is then -inf for every row, the rescale
     // test mx > m + kThr is false and every P is 2^(-inf - m) = 0 with m finite -- tile 0 holds
-    // key 0, which every row sees, so m is finite from the prologue on.
+    // key 0, which every row sees, so m is finite from the prologue on.  (KVLEN: a row may see no
+    // key of tile 0, or none at all; m then starts at a finite floor, see the prologue.)
     auto cmask = [&](int t, f32x16 (&s)[RB][NKB]) {
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             int last = (int)q_row0 + 32 * r;  // last visible key of this lane's row
-            if constexpr (TAIL) last = last < nkv - 1 ? last : nkv - 1;
+            if constexpr (KVLEN) {  // bottom-right aligned; -1: the row sees no key
+                const int64_t last_k = q_row0 + 32 * r + kv_s;
+                last = (int)(last_k < -1 ? -1 : last_k < nkv - 1 ? last_k : nkv - 1);
+            } else if constexpr (TAIL) {
+                last = last < nkv - 1 ? last : nkv - 1;
+            }
             const int lim = last - t * kBK;   // ... relative to the tile
 #pragma unroll
             for (int b2 = 0; b2 < NKB; ++b2)
@@ -730,15 +787,24 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     qk(kring, sa);
     // (causal: the first KV tile that crosses the diagonal; tile 0 does only in query tile 0)
     constexpr int ND = kBQ / kBK;
-    const int td0 = CAUSAL ? qt * ND : 0;
+    // (KVLEN: the tile that holds key s + kBQ qt, the last one the tile's first row sees, is the
+    // first that can cross -- any tile, odd ones too.  Masking a tile below the diagonal changes
+    // nothing, so the masked steps start at the even tile at or below it and the steps keep
+    // their parity; up to ND + 2 tiles are masked instead of ND.)
+    const int kv_d0 = KVLEN ? (int)((kv_s + q_tile0 > 0 ? kv_s + q_tile0 : 0) / kBK) & ~1 : 0;
+    const int td0 = KVLEN ? kv_d0 : CAUSAL ? qt * ND : 0;
     if constexpr (CAUSAL) {
         if (td0 == 0) cmask(0, sa);
     } else if constexpr (TAIL) mask(0, sa);
     rowmax(sa, mx);
     // the reference max starts at tile 0's row max (every tile holds a valid key): step 0
     // then never takes the rescale branch that a -inf start would force on every workgroup
+    // (KVLEN, causal: a row above the diagonal of every tile so far has the row max -inf.  Its
+    // reference max stays at a finite floor, so that P = 2^(-inf - m) = 0 and the rescale factor
+    // 2^(m - m_new) = 0 once a key shows up, not NaN; the epilogue guards l = 0.)
+    constexpr float kMFloor = -1e30f;
 #pragma unroll
-    for (int r = 0; r < RB; ++r) m[r] = mx[r];
+    for (int r = 0; r < RB; ++r) m[r] = KVLEN && CAUSAL ? fmaxf(mx[r], kMFloor) : mx[r];
     __syncthreads();  // K slot 0 is rewritten by step 0's DMA of K(2)
     FA_STAMP(2);
 
@@ -774,7 +840,7 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
                 run(C1{}, CNEXTK{}, t + 1, sb, sa, mx);
                 t += 2;
             }
-            if constexpr (ND > 2) {
+            if constexpr (ND > 2 || KVLEN) {
                 for (; t + 2 < ntiles; t += 2) {
                     run(C0{}, CNEXTK{}, t, sa, sb, mx);
                     run(C1{}, CNEXTK{}, t + 1, sb, sa, mx);
@@ -1012,6 +1078,7 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         const int64_t q_row = q_row0 + 32 * r;
         const float l_tot = row_sum(r);
         float inv = 1.f / l_tot;
+        if constexpr (KVLEN && CAUSAL) inv = l_tot > 0.f ? inv : 0.f;  // a row that saw no key: zeros
         if (q_row >= Lq) continue;
         if constexpr (MODE == kFinal) {
             store_row((unsigned short*)a.o + o_head + q_row * orow, o[r], inv);

@@ -97,6 +97,15 @@ struct FwdArgs {
     const int* cu_seqlens;
     int max_seqlen;
     int64_t total_rows;
+    // varlen with key lengths of their own (fa_fwd_varlen_kv.hip): cu_seqlens / max_seqlen /
+    // total_rows then describe q and o only, and sequence b's keys are rows [cu_seqlens_k[b],
+    // cu_seqlens_k[b+1]) of k and v ([Tk, H_kv, d], total_rows_k = Tk), at most max_seqlen_k of
+    // them and, where seqused_k (int32 [B], may be null) is given, only the first seqused_k[b].
+    // (Appended: no field moved.)
+    const int* cu_seqlens_k;
+    const int* seqused_k;
+    int max_seqlen_k;
+    int64_t total_rows_k;
 };
 
 // (query tile, split, b*h) of work item w (after xcd_remap)
@@ -176,6 +185,9 @@ hipError_t launch_fwd_gqa(Elem t, int d, bool causal, const FwdArgs& a, hipStrea
 // the varlen forward (fa_fwd_varlen.hip): final mode, token-packed strided tensors, device-side
 // cu_seqlens, bf16 / fp16, causal or not, a.kv_group >= 1 (1 = MHA)
 hipError_t launch_fwd_varlen(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
+// the same with a.cu_seqlens_k / seqused_k for the key side (fa_fwd_varlen_kv.hip): Lk != Lq per
+// sequence, the causal diagonal aligned bottom-right
+hipError_t launch_fwd_varlen_kv(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
 int fwd_lds_bytes(int d);
 // compute units of the device that owns `s` (the current device for the null stream;
 // fa_capi.cpp; 256 without a device)

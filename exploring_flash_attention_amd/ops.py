@@ -311,7 +311,8 @@ def _varlen_strides(ts, d):
 
 
 @_on_tensor_device
-def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
+def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None, *, cu_seqlens_k=None,
+                     max_seqlen_k=None, seqused_k=None):
     """Variable-length (token-packed) self-attention, one launch for a ragged batch
     (fa_fwd_varlen): q ``[T, H, d]``, k and v ``[T, H_kv, d]``, bfloat16 or float16, H a multiple
     of H_kv (query head h reads K/V head h // (H // H_kv)).  ``cu_seqlens``: int32 ``[B + 1]`` on
@@ -333,10 +334,34 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
 
     d = 32, 64, 128 and 256 run natively; any other d <= 256 is zero-padded to the next of them
     with the scale 1/sqrt(d) kept -- that COPIES q, k and v on every call: a convenience, not a
-    fast path.  d > 256 and float64 raise NotImplementedError."""
+    fast path.  d > 256 and float64 raise NotImplementedError.
+
+    Key lengths of their own -- chunked prefill against a prefix, prefix caching, verification of a
+    long draft, ragged cross-attention (fa_fwd_varlen_kv).  With ``cu_seqlens_k`` (int32 ``[B + 1]``
+    on q's device) and ``max_seqlen_k`` (a required int then: an upper bound of the key lengths,
+    longer ranges are truncated to it), k and v are ``[Tk, H_kv, d]`` with any Tk, sequence b's keys
+    are rows ``cu_seqlens_k[b] : cu_seqlens_k[b+1]`` of them, and ``cu_seqlens`` / ``max_seqlen``
+    describe q and the output only.  ``seqused_k`` (int32 ``[B]`` on q's device, only together with
+    ``cu_seqlens_k``) cuts sequence b's keys to the first ``seqused_k[b]`` rows of its range, clamped
+    to ``[0, range]`` on the device: a padded ``[B, Lmax, H_kv, d]`` cache is read in place as
+    ``cache.view(B * Lmax, H_kv, d)`` with ``cu_seqlens_k = arange(B + 1) * Lmax``.  With len_q query
+    and len_k key tokens and s = len_k - len_q, every query row sees all len_k keys, or with
+    ``causal=True`` position i sees keys j <= i + s -- the diagonal is aligned bottom-right, as in
+    attention_decode.  A row that sees no key (len_k = 0; causal with s < 0 and i < -s) is written
+    as zeros, never NaN.  Nothing is read on the host; the key side is clamped on the device like
+    the query side, and k / v are addressed in place under the rules above with strides of their
+    own.  With all three left None the call is the self-attention form above, unchanged."""
     # (shapes and dtypes first, so that a malformed call is named as such wherever its tensors live)
-    for name, t in (("q", q), ("k", k), ("v", v), ("cu_seqlens", cu_seqlens)):
-        if not isinstance(t, torch.Tensor):
+    kv_lens = cu_seqlens_k is not None
+    if seqused_k is not None and not kv_lens:
+        raise ValueError("seqused_k is only valid together with cu_seqlens_k")
+    if max_seqlen_k is not None and not kv_lens:
+        raise ValueError("max_seqlen_k is only valid together with cu_seqlens_k")
+    if kv_lens and max_seqlen_k is None:
+        raise ValueError("cu_seqlens_k needs max_seqlen_k (an upper bound of the key lengths)")
+    for name, t in (("q", q), ("k", k), ("v", v), ("cu_seqlens", cu_seqlens), ("cu_seqlens_k", cu_seqlens_k),
+                    ("seqused_k", seqused_k)):
+        if not isinstance(t, torch.Tensor) and not (t is None and name in ("cu_seqlens_k", "seqused_k")):
             raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dim() != 3:
@@ -345,8 +370,9 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
         raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16 or float16)")
     if k.shape != v.shape:
         raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} must have the same shape")
-    if q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on the tokens T or d")
+    if (q.shape[0] != k.shape[0] and not kv_lens) or q.shape[2] != k.shape[2]:
+        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on the tokens T or d"
+                         " (a k / v token count of its own needs cu_seqlens_k)")
     T, H, d = q.shape
     Hkv = k.shape[1]
     if Hkv <= 0 or H % Hkv:
@@ -354,10 +380,26 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
     if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1:
         raise ValueError(f"cu_seqlens must be an int32 tensor of shape (B + 1,), got {cu_seqlens.dtype} "
                          f"{tuple(cu_seqlens.shape)}")
+    if kv_lens:
+        B1 = cu_seqlens.numel()
+        if cu_seqlens_k.dtype != torch.int32 or cu_seqlens_k.dim() != 1 or cu_seqlens_k.numel() != B1:
+            raise ValueError(f"cu_seqlens_k must be an int32 tensor of shape (B + 1,) = ({B1},), got "
+                             f"{cu_seqlens_k.dtype} {tuple(cu_seqlens_k.shape)}")
+        if seqused_k is not None and (seqused_k.dtype != torch.int32 or seqused_k.dim() != 1
+                                      or seqused_k.numel() != B1 - 1):
+            raise ValueError(f"seqused_k must be an int32 tensor of shape (B,) = ({B1 - 1},), got {seqused_k.dtype} "
+                             f"{tuple(seqused_k.shape)}")
+        max_seqlen_k = int(max_seqlen_k)
+        if max_seqlen_k < 0:
+            raise ValueError(f"max_seqlen_k={max_seqlen_k} must not be negative")
     _check_tensor("q", q, ndim=3, strided=True)
     _check_tensor("k", k, q.dtype, q.device, ndim=3, strided=True)
     _check_tensor("v", v, q.dtype, q.device, ndim=3, strided=True)
     _check_tensor("cu_seqlens", cu_seqlens, torch.int32, q.device, ndim=1)
+    if kv_lens:
+        _check_tensor("cu_seqlens_k", cu_seqlens_k, torch.int32, q.device, ndim=1)
+        if seqused_k is not None:
+            _check_tensor("seqused_k", seqused_k, torch.int32, q.device, ndim=1)
     B = cu_seqlens.numel() - 1
     max_seqlen = int(max_seqlen)
     if max_seqlen < 0:
@@ -372,6 +414,12 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
     D = kernel_head_dim(d)
     if D != d:
         q, k, v = (_pad_d(t, D) for t in (q, k, v))
+    Tk = k.shape[0]
+    if kv_lens and (Tk == 0 or max_seqlen_k == 0):
+        # no key anywhere: every row of a sequence is zeros (the kernel's rule, total_tokens_k = 0);
+        # k and v are never read, one row stands in for their null pointers
+        k = v = torch.empty((1, Hkv, D), dtype=q.dtype, device=q.device)
+        Tk, max_seqlen_k = 0, 1
     st = _varlen_strides((q, k, o), D) if D == d and k.stride() == v.stride() else None
     if st is None:
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
@@ -385,6 +433,12 @@ def attention_varlen(q, k, v, cu_seqlens, max_seqlen, causal=False, out=None):
         st = _varlen_strides((q, k, op), D)
     else:
         op = o
+    if kv_lens:
+        _launched(lib().fa_fwd_varlen_kv(_ptr(q), _ptr(k), _ptr(v), _ptr(op), _ptr(cu_seqlens), _ptr(cu_seqlens_k),
+                                         None if seqused_k is None else _ptr(seqused_k), B, T, Tk, max_seqlen,
+                                         max_seqlen_k, H, Hkv, D, st[0], st[1], st[2], 1.0 / d ** 0.5,
+                                         _lib.FA_FWD_CAUSAL if causal else 0, _DTYPES[q.dtype], _stream(q)))
+        return _unpad_into(op, o, d)
     _launched(lib().fa_fwd_varlen(_ptr(q), _ptr(k), _ptr(v), _ptr(op), _ptr(cu_seqlens), B, T, max_seqlen, H, Hkv, D,
                                   st[0], st[1], st[2], 1.0 / d ** 0.5, _lib.FA_FWD_CAUSAL if causal else 0,
                                   _DTYPES[q.dtype], _stream(q)))

@@ -87,7 +87,8 @@ typedef enum fa_dtype {
  *          fa_fwd_v1_gqa and FA_FWD_CAUSAL added the same way; then fa_fwd_decode_plan and
  *          fa_fwd_decode (KV-cache decode), again additions only; then fa_fwd_decode_paged (the
  *          same forward through a block table), an addition only; then fa_fwd_varlen (token-packed
- *          ragged batches through a device-side cu_seqlens), an addition only.
+ *          ragged batches through a device-side cu_seqlens), an addition only; then
+ *          fa_fwd_varlen_kv (the same with key lengths of their own), an addition only.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -188,6 +189,33 @@ int fa_fwd_varlen(const void* q, const void* k, const void* v, void* o, const in
                   int64_t B, int64_t total_tokens, int64_t max_seqlen, int64_t H, int64_t H_kv, int64_t d,
                   const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
                   double softmax_scale, unsigned flags, int dtype, void* stream);
+/* fa_fwd_varlen with key lengths of their own: chunked prefill against a prefix, prefix caching,
+ * verification of a long draft, ragged cross-attention.  q and o are [total_tokens, H, d] and
+ * cu_seqlens / max_seqlen describe them as above; k and v are [total_tokens_k, H_kv, d] and
+ * cu_seqlens_k (int32 [B + 1] on the device) says which of their rows are sequence b's keys, at
+ * most max_seqlen_k of them (longer ranges are truncated).  seqused_k, int32 [B] on the device or
+ * NULL, cuts sequence b's keys to the first seqused_k[b] rows of its range -- a padded
+ * [B, Lmax, H_kv, d] cache is read in place as [B * Lmax, H_kv, d] with cu_seqlens_k[b] = b * Lmax.
+ * Clamped on the device like the query side, in 64-bit arithmetic:
+ *   start_k = clamp(cu_k[b], 0, total_tokens_k),
+ *   len_k   = clamp(cu_k[b+1] - start_k, 0, min(max_seqlen_k, total_tokens_k - start_k)),
+ *   len_k   = min(len_k, max(seqused_k[b], 0))   where seqused_k is given,
+ * so start_k + len_k <= total_tokens_k whatever the arrays hold, and every K / V read lies in rows
+ * [start_k, start_k + len_k).  With len_q the query length and s = len_k - len_q, query position
+ * i sees every key, or with FA_FWD_CAUSAL keys j <= i + s: the diagonal is aligned bottom-right,
+ * as in fa_fwd_decode.  A row that sees no key (len_k = 0; causal with s < 0 and i < -s) is
+ * written as zeros.  Rows of o that belong to no sequence are never written.  The grid is the
+ * query side's, B * H * ceil(max_seqlen / 128).  kv_strides address k and v as in fa_fwd_varlen.
+ * Errors as fa_fwd_varlen, and FA_ERR_INVALID_ARG for a null or misaligned cu_seqlens_k, a
+ * misaligned seqused_k, max_seqlen_k <= 0, total_tokens_k < 0; FA_ERR_UNSUPPORTED for
+ * total_tokens_k > 2^31 - 1.  k and v must be non-null even when total_tokens_k == 0 (they are not
+ * read then).  With cu_seqlens_k = cu_seqlens on the same tokens the result is fa_fwd_varlen's,
+ * bit for bit.  fa_last_kernels: "fa_fwd_kernel<final, varlen, kv[, causal][, gqa]>". */
+int fa_fwd_varlen_kv(const void* q, const void* k, const void* v, void* o, const int32_t* cu_seqlens,
+                     const int32_t* cu_seqlens_k, const int32_t* seqused_k, int64_t B, int64_t total_tokens,
+                     int64_t total_tokens_k, int64_t max_seqlen, int64_t max_seqlen_k, int64_t H, int64_t H_kv,
+                     int64_t d, const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
+                     double softmax_scale, unsigned flags, int dtype, void* stream);
 /* fa_fwd_v1_scaled on strided tensors.  q_strides, kv_strides (shared by k and v) and
  * o_strides each point to three element strides {batch, head, row} of a [B, H, L, d] view
  * whose d is contiguous -- e.g. a [B, L, H, d] tensor is {L*H*d, d, H*d} -- or are NULL for
