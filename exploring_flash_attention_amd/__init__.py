@@ -16,6 +16,9 @@ read in place through an int32 block table (page_size a multiple of 64, d = 64 /
 ``attention_varlen`` is the prefill forward of a ragged batch: token-packed ``[T, H, d]`` q and
 ``[T, H_kv, d]`` k / v with a device-side int32 ``cu_seqlens``, one launch, no padding, causal
 or not (bf16 / fp16, d <= 256), a slice of a fused QKV projection read in place;
+``attention_varlen_paged`` is that forward with the keys in the paged pool (chunked prefill against
+the cache ``attention_decode_paged`` reads, no gather) and ``kv_cache_append_paged`` writes a
+chunk's new K / V into the pool's pages;
 every other surface is non-causal with H_kv = H and Lq = Lk, as the reference is.
 
 There is no CPU fallback: every entry point raises if the HIP library is not built or no
@@ -23,13 +26,15 @@ ROCm device is present.
 """
 from . import ops  # noqa: F401
 from .ops import (attention_decode, attention_decode_paged, attention_partial, attention_tiled_d,  # noqa: F401
-                  attention_v1, attention_v2, attention_varlen, combine, kernel_geometry)
+                  attention_v1, attention_v2, attention_varlen, attention_varlen_paged, combine,
+                  kernel_geometry, kv_cache_append_paged)
 from .tiled_d import flash_attention_v1_tiled_d  # noqa: F401
 from .v1 import flash_attention_v1  # noqa: F401
 from .v2 import flash_attention_v2  # noqa: F401
 
 __all__ = ["ops", "attention_v1", "attention_tiled_d", "attention_v2", "attention_partial",
-           "attention_decode", "attention_decode_paged", "attention_varlen",
+           "attention_decode", "attention_decode_paged", "attention_varlen", "attention_varlen_paged",
+           "kv_cache_append_paged",
            "combine", "kernel_geometry", "flash_attention_v1", "flash_attention_v1_tiled_d",
            "flash_attention_v2"]
 __version__ = "0.1.0"

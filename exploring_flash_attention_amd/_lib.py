@@ -48,6 +48,10 @@ SIGNATURES = {
                            ctypes.c_uint, _I, _P]),
     "fa_fwd_varlen_kv": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P,
                               ctypes.c_double, ctypes.c_uint, _I, _P]),
+    "fa_fwd_varlen_paged": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64,
+                                 _P, _P, _P, ctypes.c_double, ctypes.c_uint, _I, _P]),
+    "fa_kv_append_paged": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64,
+                                _P, _P, _I, _P]),
     "fa_fwd_v1_ex": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, ctypes.c_double, _I, _P]),
     "fa_fwd_v1_tiled_d": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
     "fa_fwd_v1_tiled_d_scaled": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _I, ctypes.c_double, _I, _P]),

@@ -617,6 +617,191 @@ int fa_fwd_varlen_kv(const void* q, const void* k, const void* v, void* o, const
                            flags, dtype, stream);
 }
 
+// What fa_fwd_varlen_paged and fa_kv_append_paged share: the pool, the table and the arrays that
+// describe a sequence's place in them.  st3 receives the {block, head, row} strides in use.
+static int paged_pool_check(const char* who, const int32_t* cu_seqlens, const int32_t* block_table,
+                            const int32_t* seqused_k, int64_t max_seqlen_k, int64_t H_kv, int64_t d, int64_t num_blocks,
+                            int64_t page_size, int64_t table_stride, const int64_t* cache_strides, int64_t* st3) {
+    if (!cu_seqlens || ((uintptr_t)cu_seqlens & 3))
+        return fail(FA_ERR_INVALID_ARG, "%s: cu_seqlens must be non-null and 4-byte aligned", who);
+    if (!block_table || ((uintptr_t)block_table & 3))
+        return fail(FA_ERR_INVALID_ARG, "%s: block_table must be non-null and 4-byte aligned", who);
+    if (!seqused_k || ((uintptr_t)seqused_k & 3))
+        return fail(FA_ERR_INVALID_ARG, "%s: seqused_k must be non-null and 4-byte aligned", who);
+    if (num_blocks <= 0 || num_blocks > INT32_MAX)
+        return fail(FA_ERR_INVALID_ARG, "%s: num_blocks=%lld must be positive (and fit the int32 table)", who,
+                    (long long)num_blocks);
+    if (page_size <= 0) return fail(FA_ERR_INVALID_ARG, "%s: page_size=%lld must be positive", who, (long long)page_size);
+    // a KV tile (64 keys; 32 at d = 256) must lie inside one page: its descriptors cover one block
+    if (page_size % 64)
+        return fail(FA_ERR_UNSUPPORTED, "%s: page_size=%lld is not a multiple of 64 keys (pages of 16 / 32 keys have "
+                    "no kernel)", who, (long long)page_size);
+    if (page_size > (int64_t)1 << 30)
+        return fail(FA_ERR_UNSUPPORTED, "%s: page_size=%lld exceeds 2^30", who, (long long)page_size);
+    if (max_seqlen_k <= 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen_k=%lld must be positive", who, (long long)max_seqlen_k);
+    if (max_seqlen_k > (int64_t)0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "%s: max_seqlen_k=%lld exceeds 2^31-1 (seqused_k is int32)", who,
+                    (long long)max_seqlen_k);
+    if (table_stride < (max_seqlen_k + page_size - 1) / page_size)
+        return fail(FA_ERR_INVALID_ARG, "%s: table_stride=%lld is below ceil(max_seqlen_k / page_size) = %lld pages", who,
+                    (long long)table_stride, (long long)((max_seqlen_k + page_size - 1) / page_size));
+    const int64_t contig[3] = {page_size * H_kv * d, d, H_kv * d};  // [num_blocks, page_size, H_kv, d]
+    for (int i = 0; i < 3; ++i) {
+        st3[i] = cache_strides ? cache_strides[i] : contig[i];
+        if (st3[i] <= 0 || st3[i] % 8)
+            return fail(FA_ERR_INVALID_ARG, "%s: cache_strides stride[%d]=%lld must be positive and a multiple of 8 "
+                        "elements", who, i, (long long)st3[i]);
+    }
+    if (st3[2] < d)
+        return fail(FA_ERR_INVALID_ARG, "%s: cache_strides row stride %lld < d=%lld", who, (long long)st3[2], (long long)d);
+    if (st3[2] > (int64_t)1 << 20)
+        return fail(FA_ERR_UNSUPPORTED, "%s: cache_strides row stride %lld exceeds 2^20 elements", who, (long long)st3[2]);
+    return FA_OK;
+}
+
+// {token, head} strides of a token-packed tensor (NULL: contiguous [T, heads, d]) into out[2]
+static int token_strides_check(const char* who, const char* name, const int64_t* strides, int64_t heads, int64_t d,
+                               int64_t* out) {
+    out[0] = strides ? strides[0] : heads * d;
+    out[1] = strides ? strides[1] : d;
+    for (int i = 0; i < 2; ++i)
+        if (out[i] <= 0 || out[i] % 8)
+            return fail(FA_ERR_INVALID_ARG, "%s: %s stride[%d]=%lld must be positive and a multiple of 8 elements", who,
+                        name, i, (long long)out[i]);
+    if (out[0] < d)
+        return fail(FA_ERR_INVALID_ARG, "%s: %s token stride %lld < d=%lld", who, name, (long long)out[0], (long long)d);
+    if (out[0] > (int64_t)1 << 20)
+        return fail(FA_ERR_UNSUPPORTED, "%s: %s token stride %lld exceeds 2^20 elements", who, name, (long long)out[0]);
+    return FA_OK;
+}
+
+int fa_fwd_varlen_paged(const void* q, const void* k_cache, const void* v_cache, void* o, const int32_t* cu_seqlens,
+                        const int32_t* block_table, const int32_t* seqused_k, int64_t B, int64_t total_tokens,
+                        int64_t max_seqlen, int64_t max_seqlen_k, int64_t H, int64_t H_kv, int64_t d, int64_t num_blocks,
+                        int64_t page_size, int64_t table_stride, const int64_t* q_strides, const int64_t* cache_strides,
+                        const int64_t* o_strides, double softmax_scale, unsigned flags, int dtype, void* stream) {
+    static const char* const who = "varlen paged";
+    fa::Elem e;
+    if (flags & ~FA_FWD_CAUSAL)
+        return fail(FA_ERR_INVALID_ARG, "%s: unknown flags 0x%x (0 or FA_FWD_CAUSAL)", who, flags);
+    if (B <= 0) return fail(FA_ERR_INVALID_ARG, "%s: B=%lld must be positive", who, (long long)B);
+    if (total_tokens < 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: total_tokens=%lld must not be negative", who, (long long)total_tokens);
+    if (max_seqlen <= 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen=%lld must be positive", who, (long long)max_seqlen);
+    if (H <= 0 || d <= 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: H=%lld and d=%lld must be positive", who, (long long)H, (long long)d);
+    if (H_kv <= 0 || H_kv > H || H % H_kv != 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: H_kv=%lld must be positive and divide H=%lld", who, (long long)H_kv,
+                    (long long)H);
+    if (!supported_d(d))
+        return fail(FA_ERR_UNSUPPORTED, "%s: head dim d=%lld has no varlen kernel (32, 64, 128, 256 only)", who,
+                    (long long)d);
+    if (int st = check_dtype(dtype, &e)) return st;
+    if (e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "%s: FA_DTYPE_FP64 has no varlen kernel (bf16 / fp16 only)", who);
+    if (int st = check_ptrs(q, k_cache, v_cache, o)) return st;
+    int64_t cst[3], qst[2], ost[2];
+    if (int st = paged_pool_check(who, cu_seqlens, block_table, seqused_k, max_seqlen_k, H_kv, d, num_blocks, page_size,
+                                  table_stride, cache_strides, cst))
+        return st;
+    if (total_tokens > (int64_t)0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "%s: total_tokens=%lld exceeds 2^31-1 (cu_seqlens is int32)", who,
+                    (long long)total_tokens);
+    // (a length beyond the tokens is clamped on the device anyway: the grid need not cover it)
+    const int64_t msl = max_seqlen < total_tokens ? max_seqlen : total_tokens;
+    const int64_t nqt = (msl + fa::kBQ - 1) / fa::kBQ;
+    if (B > (int64_t)0x7fffffff || H > (int64_t)0x7fffffff || B * H >= (int64_t)1 << 31 ||
+        B * H * (nqt > 0 ? nqt : 1) >= (int64_t)1 << 31)
+        return fail(FA_ERR_UNSUPPORTED, "%s: grid of B * H * ceil(max_seqlen / %d) = %lld * %lld * %lld workgroups "
+                    "exceeds 2^31-1", who, fa::kBQ, (long long)B, (long long)H, (long long)nqt);
+    if (int st = token_strides_check(who, "q", q_strides, H, d, qst)) return st;
+    if (int st = token_strides_check(who, "o", o_strides, H, d, ost)) return st;
+    fa::FwdArgs a = base_args(q, k_cache, v_cache, o, B * H, msl, msl, d, e);
+    if (int s2 = apply_scale(a, softmax_scale)) return s2;
+    if (total_tokens == 0) {  // no rows: nothing to launch
+        kernels_begin();
+        return ok();
+    }
+    a.nqt = (int)nqt;
+    a.H = H;
+    a.kv_group = (int)(H / H_kv);
+    a.strided = 1;
+    a.q_stride[2] = qst[0]; a.q_stride[1] = qst[1];
+    a.o_stride[2] = ost[0]; a.o_stride[1] = ost[1];
+    a.k_stride[2] = cst[2]; a.k_stride[1] = cst[1];
+    a.block_stride = cst[0];
+    a.cu_seqlens = cu_seqlens;
+    a.max_seqlen = (int)msl;
+    a.total_rows = total_tokens;
+    a.seqused_k = seqused_k;
+    a.max_seqlen_k = (int)max_seqlen_k;
+    a.block_table = block_table;
+    a.table_stride = table_stride;
+    a.page_size = (int)page_size;
+    a.num_blocks = (int)num_blocks;
+    kernels_begin();
+    if (hipError_t he = fa::launch_fwd_varlen_paged(e, (int)d, (flags & FA_FWD_CAUSAL) != 0, a, (hipStream_t)stream))
+        return hip_fail(he, "fa_fwd_varlen_paged launch");
+    return ok();
+}
+
+int fa_kv_append_paged(const void* k_new, const void* v_new, void* k_cache, void* v_cache, const int32_t* cu_seqlens,
+                       const int32_t* block_table, const int32_t* seqused_k, int64_t B, int64_t total_tokens,
+                       int64_t max_seqlen, int64_t max_seqlen_k, int64_t H_kv, int64_t d, int64_t num_blocks,
+                       int64_t page_size, int64_t table_stride, const int64_t* new_strides, const int64_t* cache_strides,
+                       int dtype, void* stream) {
+    static const char* const who = "kv append";
+    fa::Elem e;
+    if (B <= 0) return fail(FA_ERR_INVALID_ARG, "%s: B=%lld must be positive", who, (long long)B);
+    if (total_tokens < 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: total_tokens=%lld must not be negative", who, (long long)total_tokens);
+    if (max_seqlen <= 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: max_seqlen=%lld must be positive", who, (long long)max_seqlen);
+    if (H_kv <= 0 || d <= 0)
+        return fail(FA_ERR_INVALID_ARG, "%s: H_kv=%lld and d=%lld must be positive", who, (long long)H_kv, (long long)d);
+    if (d % 8 || d > 256)
+        return fail(FA_ERR_UNSUPPORTED, "%s: head dim d=%lld is not a multiple of 8 up to 256", who, (long long)d);
+    if (int st = check_dtype(dtype, &e)) return st;
+    if (e == fa::Elem::F64)
+        return fail(FA_ERR_UNSUPPORTED, "%s: FA_DTYPE_FP64 pools are not supported (bf16 / fp16 only)", who);
+    if (int st = check_ptrs(k_new, v_new, k_cache, v_cache)) return st;
+    int64_t cst[3], nst[2];
+    if (int st = paged_pool_check(who, cu_seqlens, block_table, seqused_k, max_seqlen_k, H_kv, d, num_blocks, page_size,
+                                  table_stride, cache_strides, cst))
+        return st;
+    if (total_tokens > (int64_t)0x7fffffff)
+        return fail(FA_ERR_UNSUPPORTED, "%s: total_tokens=%lld exceeds 2^31-1 (cu_seqlens is int32)", who,
+                    (long long)total_tokens);
+    const int64_t msl = max_seqlen < total_tokens ? max_seqlen : total_tokens;
+    const int64_t nrb = (msl + fa::kAppendRows - 1) / fa::kAppendRows;
+    if (B > (int64_t)0x7fffffff || H_kv > (int64_t)0x7fffffff || B * H_kv >= (int64_t)1 << 31 ||
+        B * H_kv * (nrb > 0 ? nrb : 1) >= (int64_t)1 << 31)
+        return fail(FA_ERR_UNSUPPORTED, "%s: grid of B * ceil(max_seqlen / %d) * H_kv = %lld * %lld * %lld workgroups "
+                    "exceeds 2^31-1", who, fa::kAppendRows, (long long)B, (long long)nrb, (long long)H_kv);
+    if (int st = token_strides_check(who, "k_new/v_new", new_strides, H_kv, d, nst)) return st;
+    kernels_begin();
+    if (total_tokens == 0) return ok();  // no rows: nothing to launch
+    fa::AppendArgs a{};
+    a.k_new = k_new; a.v_new = v_new; a.k_cache = k_cache; a.v_cache = v_cache;
+    a.cu_seqlens = cu_seqlens; a.seqused_k = seqused_k; a.block_table = block_table;
+    a.total_rows = total_tokens;
+    a.B = (int)B;
+    a.max_seqlen = (int)msl;
+    a.nrb = (int)nrb;
+    a.Hkv = (int)H_kv;
+    a.chunks = (int)(d / 8);
+    a.new_stride[0] = nst[0]; a.new_stride[1] = nst[1];
+    for (int i = 0; i < 3; ++i) a.cache_stride[i] = cst[i];
+    a.table_stride = table_stride;
+    a.max_seqlen_k = max_seqlen_k;
+    a.page_size = (int)page_size;
+    a.num_blocks = (int)num_blocks;
+    if (hipError_t he = fa::launch_kv_append(a, (hipStream_t)stream)) return hip_fail(he, "fa_kv_append_paged launch");
+    return ok();
+}
+
 int fa_fwd_v1_tiled_d(const void* q, const void* k, const void* v, void* o, int64_t B, int64_t H,
                       int64_t L, int64_t d, int d_tile_qk, int d_tile_v, int dtype, void* stream) {
     return fa_fwd_v1_tiled_d_scaled(q, k, v, o, B, H, L, d, d_tile_qk, d_tile_v,

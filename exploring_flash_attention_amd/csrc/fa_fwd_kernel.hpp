@@ -1,8 +1,8 @@
 // fa_fwd_kernel.hpp -- flash-attention forward kernel for MI355X (gfx950 / CDNA4), included by
 // fa_fwd.hip (contiguous [B,H,L,d] launches), fa_fwd_strided.hip (strided launches),
 // fa_fwd_causal.hip (the causal instantiations), fa_fwd_gqa.hip (grouped-query),
-// fa_fwd_varlen.hip (token-packed ragged batches) and fa_fwd_varlen_kv.hip (the same with key
-// lengths of their own).
+// fa_fwd_varlen.hip (token-packed ragged batches), fa_fwd_varlen_kv.hip (the same with key
+// lengths of their own) and fa_fwd_varlen_paged.hip (those keys in a paged pool).
 //
 // One kernel template serves the three reference kernel families:
 //   final mode   (MODE=kFinal): FA-v1 fused / d-tiled forward
@@ -120,13 +120,21 @@ namespace fa {
 // causal diagonal is aligned bottom-right, query row i sees keys j <= i + s, s = Lk - Lq, so the
 // first tile that crosses the diagonal is no multiple of kBQ / kBK any more; a row may see no key
 // at all (s < 0, or Lk = 0) and is then written as zeros.
+// PAGED (KVLEN only; instantiated in fa_fwd_varlen_paged.hip): k / v are pools of a.num_blocks blocks
+// of a.page_size keys (a multiple of the KV tile), strides {block, head, row} in a.block_stride,
+// a.k_stride[1], a.k_stride[2].  Key j of sequence b is row j % page_size of block
+// clamp(block_table[b * table_stride + j / page_size], 0, num_blocks - 1); the sequence has
+// clamp(seqused_k[b], 0, max_seqlen_k) keys from logical key 0 on, and there is no cu_seqlens_k.
+// Tile t starts at key t * kBK and lies inside one page, so only the BASE of its DMA descriptor
+// changes (dma_tile_paged); its length, the tiles, their order and all arithmetic are KVLEN's.
 template <typename T, typename PT, int D, int MODE, bool TAIL, bool STRIDED = false, bool CAUSAL = false,
-          bool GQA = false, bool VARLEN = false, bool KVLEN = false>
+          bool GQA = false, bool VARLEN = false, bool KVLEN = false, bool PAGED = false>
 __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void fa_fwd_kernel(FwdArgs a) {
     static_assert(!CAUSAL || (MODE == kFinal && (!STRIDED || VARLEN)), "causal: final mode, contiguous tensors");
     static_assert(!GQA || (MODE == kFinal && (!STRIDED || VARLEN)), "GQA: final mode, contiguous tensors");
     static_assert(!VARLEN || (MODE == kFinal && TAIL && STRIDED && GQA), "varlen: final mode, runtime lengths, strided rows");
     static_assert(!KVLEN || VARLEN, "separate key lengths: a varlen variant");
+    static_assert(!PAGED || KVLEN, "paged keys: a variant of the separate key lengths");
     using M = Mma<T>;
     using v8 = typename M::v8;
     constexpr int RB = kRB;                   // 32-row query blocks per wave
@@ -187,7 +195,12 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     // Tk - start_k)), then at most clamp(seqused_k[b], 0, ..) -- start_k + len_k <= Tk whatever the
     // arrays hold, and every K / V descriptor below covers rows of [start_k, start_k + len_k) only.
     int vk_start = 0, vk_len = 0;
-    if constexpr (KVLEN) {
+    if constexpr (PAGED) {
+        // keys [0, len_k) of the sequence's pages, len_k = clamp(seqused_k[b], 0, max_seqlen_k)
+        const unsigned b = (unsigned)bh / (unsigned)a.H;
+        const int u = a.seqused_k[b];
+        vk_len = __builtin_amdgcn_readfirstlane(u < 0 ? 0 : u < a.max_seqlen_k ? u : a.max_seqlen_k);
+    } else if constexpr (KVLEN) {
         const unsigned b = (unsigned)bh / (unsigned)a.H;
         const int64_t nt = a.total_rows_k;  // Tk
         const int64_t c0 = a.cu_seqlens_k[b], c1 = a.cu_seqlens_k[b + 1];
@@ -303,6 +316,31 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         const int ch = 4 * (rem / 512) + (((rem % 64) / 16) ^ ((row >> 2) & 3));
         dma_src[i] = row * krb + ch * 16;
     }
+    // PAGED: the block of tile t comes from the sequence's table row by a scalar load (constant
+    // address space: the table is not written while the kernel runs).  Scalar loads and LDS reads
+    // share lgkmcnt, so an entry is fetched well ahead of its DMA: the tiles are taken in order,
+    // a cursor (page, tile in page) walks them, and step t issues the load for tile t + 3 behind
+    // its DMAs of K(t+2) and V(t+1) -- the wait for it falls behind the step's barrier.  The
+    // cursor's page stops at the last page that holds a key below kv_end: entries past it are
+    // never read (tiles there have empty descriptors, whatever their base).
+    typedef __attribute__((address_space(4))) const int* table_ptr;
+    table_ptr ptbl = nullptr;
+    int pg_tiles = 1, pg_last = 0, pc_page = 0, pc_in = 0;
+    int pe1 = 0, pr1 = 0, pe2 = 0, pr2 = 0;  // raw table entry and first row in its page of tiles t+1, t+2
+    if constexpr (PAGED) {
+        ptbl = (table_ptr)(a.block_table + (int64_t)((unsigned)bh / (unsigned)a.H) * a.table_stride);
+        pg_tiles = __builtin_amdgcn_readfirstlane(a.page_size / kBK);
+        pg_last = __builtin_amdgcn_readfirstlane((int)((unsigned)(nkv - 1) / (unsigned)a.page_size));  // nkv > 0 here
+    }
+    auto paged_next = [&](int& e, int& row) {
+        if constexpr (PAGED) {
+            e = ptbl[pc_page < pg_last ? pc_page : pg_last];
+            row = pc_in * kBK;
+            const bool wrap = pc_in + 1 == pg_tiles;
+            pc_in = wrap ? 0 : pc_in + 1;
+            pc_page += wrap ? 1 : 0;
+        }
+    };
     auto dma_tile = [&](const unsigned short* base, char* slot, int t) {
         // descriptor over exactly the tile's valid keys (32-bit scalar arithmetic)
         // (readfirstlane: hipcc evaluates the clamp with v_med3, and a descriptor word it
@@ -317,6 +355,23 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
         if (NDMA >= kWaves || dma_wave) {
 #pragma unroll
             for (int i = 0; i < DPW; ++i) dma16(rs, slot + (wid * DPW + i) * 1024, dma_src[i], 0);
+        }
+    };
+    // PAGED: dma_tile with the descriptor's base in the page -- table entry pe, clamped into the pool
+    // before it enters the address, and the tile's first row prow inside that block.  The length
+    // is dma_tile's: rows prow .. prow + valid - 1 lie inside the page (page_size % kBK == 0).
+    auto dma_tile_paged = [&](const unsigned short* base, char* slot, int t, int pe, int prow) {
+        if constexpr (PAGED) {
+            const int rem = nkv - t * kBK;
+            const int valid = __builtin_amdgcn_readfirstlane(rem < kBK ? (rem > 0 ? rem : 0) : kBK);
+            const int bytes = valid > 0 ? (valid - 1) * krb + ROWB : 0;
+            const int pblk = pe < 0 ? 0 : pe > a.num_blocks - 1 ? a.num_blocks - 1 : pe;
+            const int64_t toff = ((int64_t)pblk * a.block_stride + (int64_t)prow * a.k_stride[2]) * 2;
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc32((const char*)base + toff, bytes);
+            if (NDMA >= kWaves || dma_wave) {
+#pragma unroll
+                for (int i = 0; i < DPW; ++i) dma16(rs, slot + (wid * DPW + i) * 1024, dma_src[i], 0);
+            }
         }
     };
 
@@ -563,8 +618,16 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
 
         // DMA issued in the MFMA block (the scheduler spreads the pieces among the MFMAs);
         // tile counts are checked against the compile-time MORE where possible
-        if constexpr (DMAK) dma_tile(kbase, kring + P * TILEB, t + 2);
-        if constexpr (MORE) dma_tile(vbase, vring + (1 - P) * TILEB, t + 1);
+        if constexpr (PAGED) {
+            if constexpr (DMAK) dma_tile_paged(kbase, kring + P * TILEB, t + 2, pe2, pr2);
+            if constexpr (MORE) dma_tile_paged(vbase, vring + (1 - P) * TILEB, t + 1, pe1, pr1);
+            pe1 = pe2;
+            pr1 = pr2;
+            paged_next(pe2, pr2);  // tile t + 3, for the next step
+        } else {
+            if constexpr (DMAK) dma_tile(kbase, kring + P * TILEB, t + 2);
+            if constexpr (MORE) dma_tile(vbase, vring + (1 - P) * TILEB, t + 1);
+        }
         if constexpr (MORE) qk(kring + (1 - P) * TILEB, sn);
         exp_tile(sc);
         v8 pb[RB][NKB][2];
@@ -771,9 +834,19 @@ __global__ __launch_bounds__(kThreads, kernel_wps(D, MODE, TAIL, STRIDED)) void 
     };
 
     // prologue: K(0), V(0), K(1) -> LDS; S(0) = QK^T(0)
-    dma_tile(kbase, kring, 0);
-    dma_tile(vbase, vring, 0);
-    if (ntiles > 1) dma_tile(kbase, kring + TILEB, 1);
+    if constexpr (PAGED) {
+        int pe0, pr0;
+        paged_next(pe0, pr0);
+        paged_next(pe1, pr1);
+        paged_next(pe2, pr2);
+        dma_tile_paged(kbase, kring, 0, pe0, pr0);
+        dma_tile_paged(vbase, vring, 0, pe0, pr0);
+        if (ntiles > 1) dma_tile_paged(kbase, kring + TILEB, 1, pe1, pr1);
+    } else {
+        dma_tile(kbase, kring, 0);
+        dma_tile(vbase, vring, 0);
+        if (ntiles > 1) dma_tile(kbase, kring + TILEB, 1);
+    }
     // Q's loads must retire here: otherwise hipcc's waitcnt pass carries them into the loop
     // header and, merging with the back edge, waits vmcnt(N) in front of every MFMA.
 #pragma unroll

@@ -106,7 +106,47 @@ struct FwdArgs {
     const int* seqused_k;
     int max_seqlen_k;
     int64_t total_rows_k;
+    // varlen with a paged key side (fa_fwd_varlen_paged.hip): k / v are pools of num_blocks blocks
+    // of page_size keys (a multiple of bk_for(d)), element strides block_stride between blocks,
+    // k_stride[1] between heads and k_stride[2] between the rows of a page.  Key j of sequence b
+    // is row j % page_size of block block_table[b * table_stride + j / page_size] (int32 on the
+    // device, clamped to [0, num_blocks - 1] there); its keys are the first seqused_k[b] (required,
+    // clamped to [0, max_seqlen_k]) and cu_seqlens_k / total_rows_k are unused.  (Appended: no
+    // field moved.)
+    const int* block_table;
+    int64_t table_stride;
+    int page_size;
+    int num_blocks;
+    int64_t block_stride;
 };
+
+// Arguments of the KV append kernel (fa_kv_append.hip): the new K / V rows of a token-packed chunk
+// ([T, H_kv, d], strides {token, head}) go into the pages of a pool (strides {block, head, row})
+// that the block table names.  cu_seqlens / max_seqlen / total_rows are clamped as the varlen
+// forward clamps its query side; seqused_k[b] is the key count AFTER the append, so new token i of
+// sequence b is logical key p = seqused_k[b] - len_q + i, skipped unless 0 <= p < max_seqlen_k.
+struct AppendArgs {
+    const void* k_new;
+    const void* v_new;
+    void* k_cache;
+    void* v_cache;
+    const int* cu_seqlens;
+    const int* seqused_k;
+    const int* block_table;
+    int64_t total_rows;   // T
+    int B;
+    int max_seqlen;
+    int nrb;              // row blocks per sequence = ceil(max_seqlen / kAppendRows)
+    int Hkv;
+    int chunks;           // 16-byte pieces per row = d / 8
+    int64_t new_stride[2], cache_stride[3];
+    int64_t table_stride;
+    int64_t max_seqlen_k;  // keys the table maps (at most table_stride * page_size)
+    int page_size;
+    int num_blocks;
+};
+constexpr int kAppendRows = 32;      // token rows per workgroup
+constexpr int kAppendThreads = 256;
 
 // (query tile, split, b*h) of work item w (after xcd_remap)
 __device__ __forceinline__ void decode_item(const FwdArgs& a, int w, int& qt, int& split, int64_t& bh) {
@@ -188,6 +228,11 @@ hipError_t launch_fwd_varlen(Elem t, int d, bool causal, const FwdArgs& a, hipSt
 // the same with a.cu_seqlens_k / seqused_k for the key side (fa_fwd_varlen_kv.hip): Lk != Lq per
 // sequence, the causal diagonal aligned bottom-right
 hipError_t launch_fwd_varlen_kv(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
+// the same with the keys in a paged pool behind a.block_table (fa_fwd_varlen_paged.hip): a.seqused_k
+// required, no a.cu_seqlens_k
+hipError_t launch_fwd_varlen_paged(Elem t, int d, bool causal, const FwdArgs& a, hipStream_t s);
+// a chunk's new K / V rows into the pool's pages (fa_kv_append.hip); bf16 / fp16 move alike
+hipError_t launch_kv_append(const AppendArgs& a, hipStream_t s);
 int fwd_lds_bytes(int d);
 // compute units of the device that owns `s` (the current device for the null stream;
 // fa_capi.cpp; 256 without a device)

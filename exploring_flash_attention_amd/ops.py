@@ -14,9 +14,10 @@ Reference launchers these replace (tyler-utah/exploring_flash_attention):
   attention_partial  partial_attention_kernel, flash_attention_v2/CUDA/flash_attention_v2.h:243
   combine            reduction_kernel,         flash_attention_v2/CUDA/flash_attention_v2.h:356
 attention_decode (KV-cache decode: Lq != Lk, per-sequence key lengths, GQA-packed split-KV),
-attention_decode_paged (the same on a paged pool, through a block table) and attention_varlen
-(ragged prefill batches: token-packed [T, H, d] tensors with a device-side cu_seqlens) have no
-counterpart in the reference.
+attention_decode_paged (the same on a paged pool, through a block table), attention_varlen
+(ragged prefill batches: token-packed [T, H, d] tensors with a device-side cu_seqlens),
+attention_varlen_paged (that prefill with the keys in the paged pool) and kv_cache_append_paged
+(a chunk's new K / V into the pool's pages) have no counterpart in the reference.
 """
 import contextlib
 import ctypes
@@ -863,6 +864,213 @@ def attention_decode_paged(q, k_cache, v_cache, block_table, seqlens_k=None, max
                                         0 if workspace is None else workspace.numel() * workspace.element_size(),
                                         _DTYPES[q.dtype], _stream(q)))
     return _unpad_into(op, o, d)
+
+
+VARLEN_PAGED_HEAD_DIMS = (32, 64, 128, 256)  # head dims of the paged varlen forward (a pool is not padded)
+
+
+def _paged_pool_args(who, k_cache, v_cache, dtype, device, block_table, seqused_k, B):
+    """The pool / table / key-count checks attention_varlen_paged and kv_cache_append_paged share.
+    Returns (num_blocks, page_size, H_kv, P, table_stride, cache_strides {block, head, row})."""
+    _check_tensor("k_cache", k_cache, dtype, device, strided=True)
+    _check_tensor("v_cache", v_cache, dtype, device, strided=True)
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache {tuple(k_cache.shape)} and v_cache {tuple(v_cache.shape)} must have the same shape")
+    nblk, ps, Hkv, d = k_cache.shape
+    if ps <= 0 or ps % DECODE_PAGE_MULTIPLE:
+        raise NotImplementedError(f"{who}: page_size={ps} is not a multiple of {DECODE_PAGE_MULTIPLE} keys (pages of "
+                                  "16 / 32 keys have no kernel)")
+    _check_tensor("block_table", block_table, torch.int32, device, ndim=2, strided=True)
+    if block_table.shape[0] != B:
+        raise ValueError(f"block_table must be an int32 tensor of shape ({B}, pages), got {block_table.dtype} "
+                         f"{tuple(block_table.shape)}")
+    P = block_table.shape[1]
+    if (P > 1 and block_table.stride(1) != 1) or (B > 1 and block_table.stride(0) < P):
+        raise ValueError(f"block_table rows must be contiguous and at least {P} entries apart (strides "
+                         f"{tuple(block_table.stride())})")
+    _check_tensor("seqused_k", seqused_k, torch.int32, device, ndim=1)
+    if tuple(seqused_k.shape) != (B,):
+        raise ValueError(f"seqused_k must be an int32 tensor of shape ({B},), got {seqused_k.dtype} "
+                         f"{tuple(seqused_k.shape)}")
+    st = k_cache.stride()
+    if nblk > 0 and not (st == v_cache.stride() and st[3] == 1 and all(x > 0 and x % 8 == 0 for x in st[:3])
+                         and st[1] >= d and st[1] <= 1 << 20 and k_cache.data_ptr() % 16 == 0
+                         and v_cache.data_ptr() % 16 == 0):
+        raise NotImplementedError(f"{who}: the pool is addressed in place and this view cannot be (k_cache strides "
+                                  f"{tuple(st)}, v_cache strides {tuple(v_cache.stride())}): d contiguous, shared "
+                                  "strides that are multiples of 8 elements, 16-byte aligned bases")
+    tstride = block_table.stride(0) if B > 1 else max(P, block_table.stride(0))
+    return nblk, ps, Hkv, P, tstride, (ctypes.c_int64 * 3)(st[0], st[2], st[1])
+
+
+def _check_cu_seqlens(cu_seqlens, device):
+    if not isinstance(cu_seqlens, torch.Tensor):
+        raise TypeError(f"cu_seqlens must be a torch.Tensor, got {type(cu_seqlens).__name__}")
+    if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() < 1:
+        raise ValueError(f"cu_seqlens must be an int32 tensor of shape (B + 1,), got {cu_seqlens.dtype} "
+                         f"{tuple(cu_seqlens.shape)}")
+    _check_tensor("cu_seqlens", cu_seqlens, torch.int32, device, ndim=1)
+    return cu_seqlens.numel() - 1
+
+
+@_on_tensor_device
+def attention_varlen_paged(q, k_cache, v_cache, cu_seqlens, max_seqlen, block_table, seqused_k, max_seqlen_k=None,
+                           causal=False, out=None):
+    """attention_varlen with the keys in a paged KV cache, read in place through a block table
+    (fa_fwd_varlen_paged): chunked and prefix-cached prefill against the pool attention_decode_paged
+    reads, one launch, nothing read on the host.  q ``[T, H, d]`` with ``cu_seqlens`` /
+    ``max_seqlen`` as in attention_varlen; pools k_cache, v_cache ``[num_blocks, page_size, H_kv,
+    d]``, bfloat16 or float16.  Sequence b has ``clamp(seqused_k[b], 0, max_seqlen_k)`` keys, key j
+    being row ``j % page_size`` of block ``block_table[b, j // page_size]``; with ``causal=True``
+    query position i sees keys j <= i + len_k - len_q (bottom-right aligned), and a row that sees
+    no key is written as zeros.  The result is exactly (bit for bit) ``attention_varlen(q, Kg, Vg,
+    cu_seqlens, max_seqlen, causal, cu_seqlens_k=arange(B + 1) * Lg, max_seqlen_k=max_seqlen_k,
+    seqused_k=seqused_k)`` on the cache gathered in table order into ``[B * Lg, H_kv, d]``.
+
+    ``block_table``: int32 ``[B, P]`` on q's device, last dim contiguous, any row stride >= P.  Only
+    the entries of pages that hold a key the call reads are loaded (the rest may be -1 or anything)
+    and every entry is clamped to [0, num_blocks - 1] on the device: a corrupt table gives a wrong
+    result, never an access outside the pool.  ``seqused_k``: int32 ``[B]``.  ``max_seqlen_k`` (None:
+    P * page_size): the upper bound of the key counts, at most P * page_size.
+
+    The pool is never copied and never padded: any strides are taken when d is contiguous, k_cache
+    and v_cache share strides that are multiples of 8 elements and the bases are 16-byte aligned --
+    a ``[num_blocks, H_kv, page_size, d]`` pool goes in as ``pool.transpose(1, 2)``.  Other views,
+    page_size not a multiple of 64, d other than 32 / 64 / 128 / 256 and float64 raise
+    NotImplementedError.  q and out follow attention_varlen's in-place / copy rules; rows of the
+    output that belong to no sequence keep what ``out`` holds."""
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens", cu_seqlens),
+                    ("block_table", block_table), ("seqused_k", seqused_k)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if q.dim() != 3:
+        raise ValueError(f"q must be 3-D [tokens, heads, d], got shape {tuple(q.shape)}")
+    if k_cache.dim() != 4:
+        raise ValueError(f"k_cache must be 4-D [num_blocks, page_size, H_kv, d], got shape {tuple(k_cache.shape)}")
+    if q.dtype not in _DTYPES:
+        raise ValueError(f"q dtype {q.dtype} unsupported (bfloat16 or float16)")
+    if q.shape[2] != k_cache.shape[3]:
+        raise ValueError(f"q {tuple(q.shape)} and k_cache {tuple(k_cache.shape)} disagree on d")
+    T, H, d = q.shape
+    if block_table.dtype != torch.int32 or block_table.dim() != 2:
+        raise ValueError(f"block_table must be an int32 tensor of shape (B, pages), got {block_table.dtype} "
+                         f"{tuple(block_table.shape)}")
+    if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1:
+        raise ValueError(f"seqused_k must be an int32 tensor of shape (B,), got {seqused_k.dtype} "
+                         f"{tuple(seqused_k.shape)}")
+    _check_tensor("q", q, ndim=3, strided=True)
+    B = _check_cu_seqlens(cu_seqlens, q.device)
+    if q.dtype == torch.float64:
+        raise NotImplementedError("attention_varlen_paged: float64 tensors are not supported (use bfloat16 or float16)")
+    if d not in VARLEN_PAGED_HEAD_DIMS:
+        raise NotImplementedError(f"attention_varlen_paged: head dim d={d} is not supported (32, 64, 128 or 256; a "
+                                  "pool is not padded)")
+    nblk, ps, Hkv, P, tstride, cst = _paged_pool_args("attention_varlen_paged", k_cache, v_cache, q.dtype, q.device,
+                                                      block_table, seqused_k, B)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError(f"attention_varlen_paged: H={H} query heads are not a multiple of H_kv={Hkv} K/V heads")
+    max_seqlen = int(max_seqlen)
+    if max_seqlen < 0:
+        raise ValueError(f"max_seqlen={max_seqlen} must not be negative")
+    Lk = P * ps if max_seqlen_k is None else int(max_seqlen_k)
+    if Lk < 0:
+        raise ValueError(f"max_seqlen_k={Lk} must not be negative")
+    if Lk > P * ps:
+        raise ValueError(f"max_seqlen_k={Lk} exceeds what the block table maps ({P} pages of {ps} keys)")
+    o = _out(out, q, strided=True)
+    if q.numel() == 0 or B == 0 or max_seqlen == 0:  # no rows, no sequences: nothing to launch
+        return o
+    if Lk == 0:
+        # no key anywhere: every row of a sequence is zeros (the kernel's rule).  One block of zeros
+        # and a zero key count stand in for the pool, which is never read
+        k_cache = v_cache = torch.zeros((1, ps, Hkv, d), dtype=q.dtype, device=q.device)
+        block_table = torch.zeros((B, 1), dtype=torch.int32, device=q.device)
+        seqused_k = torch.zeros((B,), dtype=torch.int32, device=q.device)
+        st = k_cache.stride()
+        nblk, tstride, Lk, cst = 1, 1, 1, (ctypes.c_int64 * 3)(st[0], st[2], st[1])
+    if nblk == 0:
+        raise ValueError("attention_varlen_paged: the pool has no blocks")
+    st = _varlen_strides((q, o), d)
+    if st is None:
+        q = q.contiguous()
+        if _varlen_strides((o,), d) is None:
+            # rows of no sequence keep what out holds: the kernel's output starts as a copy of it
+            op = torch.empty((T, H, d), dtype=q.dtype, device=q.device)
+            if out is not None:
+                op.copy_(o)
+        else:
+            op = o
+        st = _varlen_strides((q, op), d)
+    else:
+        op = o
+    _launched(lib().fa_fwd_varlen_paged(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(op), _ptr(cu_seqlens),
+                                        _ptr(block_table), _ptr(seqused_k), B, T, max_seqlen, Lk, H, Hkv, d, nblk, ps,
+                                        tstride, st[0], cst, st[1], 1.0 / d ** 0.5,
+                                        _lib.FA_FWD_CAUSAL if causal else 0, _DTYPES[q.dtype], _stream(q)))
+    return _unpad_into(op, o, d)
+
+
+@_on_tensor_device
+def kv_cache_append_paged(k_new, v_new, k_cache, v_cache, cu_seqlens, max_seqlen, block_table, seqused_k):
+    """Write a chunk's new K / V rows into the pages of a paged KV cache (fa_kv_append_paged), in
+    place, on the current stream, with nothing read on the host.  k_new, v_new ``[T, H_kv, d]``
+    (token-packed like attention_varlen's k / v: read in place under its stride rules, e.g. the K
+    and V slices of a fused QKV projection; other views are copied), pools ``[num_blocks,
+    page_size, H_kv, d]`` under attention_varlen_paged's rules, ``block_table`` int32 ``[B, P]``.
+    ``cu_seqlens`` / ``max_seqlen`` name each sequence's new tokens and are clamped on the device
+    like attention_varlen's.  ``seqused_k[b]`` is the sequence's key count AFTER the append -- pass
+    the same array to attention_varlen_paged next: new token i of a sequence with len_q new tokens
+    becomes logical key ``p = seqused_k[b] - len_q + i``, row ``p % page_size`` of block
+    ``block_table[b, p // page_size]`` (clamped to the pool).  A token with p < 0 or p >= P *
+    page_size has no page and is skipped.  Only rows that a token owns are written.
+
+    d is any multiple of 8 up to 256, bfloat16 or float16; other head dims, float64, page sizes
+    that are not multiples of 64 and pool views that cannot be addressed raise NotImplementedError."""
+    for name, t in (("k_new", k_new), ("v_new", v_new), ("k_cache", k_cache), ("v_cache", v_cache),
+                    ("cu_seqlens", cu_seqlens), ("block_table", block_table), ("seqused_k", seqused_k)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be 3-D [tokens, heads, d], got shape {tuple(t.shape)}")
+    if k_cache.dim() != 4:
+        raise ValueError(f"k_cache must be 4-D [num_blocks, page_size, H_kv, d], got shape {tuple(k_cache.shape)}")
+    if k_new.dtype not in _DTYPES:
+        raise ValueError(f"k_new dtype {k_new.dtype} unsupported (bfloat16 or float16)")
+    if k_new.shape != v_new.shape:
+        raise ValueError(f"k_new {tuple(k_new.shape)} and v_new {tuple(v_new.shape)} must have the same shape")
+    if tuple(k_new.shape[1:]) != (k_cache.shape[2], k_cache.shape[3]):
+        raise ValueError(f"k_new {tuple(k_new.shape)} and k_cache {tuple(k_cache.shape)} disagree on H_kv or d")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2:
+        raise ValueError(f"block_table must be an int32 tensor of shape (B, pages), got {block_table.dtype} "
+                         f"{tuple(block_table.shape)}")
+    if seqused_k.dtype != torch.int32 or seqused_k.dim() != 1:
+        raise ValueError(f"seqused_k must be an int32 tensor of shape (B,), got {seqused_k.dtype} "
+                         f"{tuple(seqused_k.shape)}")
+    _check_tensor("k_new", k_new, ndim=3, strided=True)
+    _check_tensor("v_new", v_new, k_new.dtype, k_new.device, ndim=3, strided=True)
+    B = _check_cu_seqlens(cu_seqlens, k_new.device)
+    T, Hkv, d = k_new.shape
+    if k_new.dtype == torch.float64:
+        raise NotImplementedError("kv_cache_append_paged: float64 tensors are not supported (use bfloat16 or float16)")
+    if d <= 0 or d % 8 or d > 256:
+        raise NotImplementedError(f"kv_cache_append_paged: head dim d={d} is not supported (a multiple of 8 up to 256)")
+    nblk, ps, _, P, tstride, cst = _paged_pool_args("kv_cache_append_paged", k_cache, v_cache, k_new.dtype,
+                                                    k_new.device, block_table, seqused_k, B)
+    max_seqlen = int(max_seqlen)
+    if max_seqlen < 0:
+        raise ValueError(f"max_seqlen={max_seqlen} must not be negative")
+    if k_new.numel() == 0 or B == 0 or max_seqlen == 0 or P == 0:  # no token that could be placed
+        return
+    if nblk == 0:
+        raise ValueError("kv_cache_append_paged: the pool has no blocks")
+    st = _varlen_strides((k_new,), d) if k_new.stride() == v_new.stride() else None
+    if st is None or _varlen_strides((v_new,), d) is None:
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+        st = _varlen_strides((k_new,), d)
+    _launched(lib().fa_kv_append_paged(_ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(cu_seqlens),
+                                       _ptr(block_table), _ptr(seqused_k), B, T, max_seqlen, P * ps, Hkv, d, nblk, ps,
+                                       tstride, st[0], cst, _DTYPES[k_new.dtype], _stream(k_new)))
 
 
 def kernel_geometry(d, dtype=torch.bfloat16):

@@ -88,7 +88,8 @@ typedef enum fa_dtype {
  *          fa_fwd_decode (KV-cache decode), again additions only; then fa_fwd_decode_paged (the
  *          same forward through a block table), an addition only; then fa_fwd_varlen (token-packed
  *          ragged batches through a device-side cu_seqlens), an addition only; then
- *          fa_fwd_varlen_kv (the same with key lengths of their own), an addition only.
+ *          fa_fwd_varlen_kv (the same with key lengths of their own), an addition only; then
+ *          fa_fwd_varlen_paged (those keys in a paged pool) and fa_kv_append_paged, additions only.
  * fa_version() returns the library's (major << 16) | (minor << 8) | patch; check it against
  * these macros at load time. */
 #define FA_MI355X_VERSION_MAJOR 0
@@ -216,6 +217,62 @@ int fa_fwd_varlen_kv(const void* q, const void* k, const void* v, void* o, const
                      int64_t total_tokens_k, int64_t max_seqlen, int64_t max_seqlen_k, int64_t H, int64_t H_kv,
                      int64_t d, const int64_t* q_strides, const int64_t* kv_strides, const int64_t* o_strides,
                      double softmax_scale, unsigned flags, int dtype, void* stream);
+/* fa_fwd_varlen_kv with the keys in a PAGED pool, read in place through a block table: chunked and
+ * prefix-cached prefill against the cache fa_fwd_decode_paged reads.  q and o are [total_tokens, H,
+ * d] and cu_seqlens / max_seqlen describe them as in fa_fwd_varlen.  k_cache and v_cache are pools
+ * of num_blocks blocks of page_size keys; a sequence's keys start at logical key 0 (there is no
+ * cu_seqlens_k), key j of sequence b is row j % page_size of block
+ *   clamp(block_table[b * table_stride + j / page_size], 0, num_blocks - 1),
+ * and it has len_k = clamp(seqused_k[b], 0, max_seqlen_k) of them.  block_table (int32, table_stride
+ * entries per sequence) and seqused_k (int32 [B], REQUIRED here) live on the device and are read
+ * there only.  Only the table entries of pages that hold a key the call reads are loaded -- the
+ * rest may be -1 or anything -- and every entry is clamped into the pool before it enters an
+ * address: a corrupt table or length gives a wrong result, never an access outside the pool.
+ *   cache_strides (shared by the pools): three element strides {block, head, row}, d contiguous,
+ *     or NULL for contiguous [num_blocks, page_size, H_kv, d]; a [num_blocks, H_kv, page_size, d]
+ *     pool is {H_kv * page_size * d, page_size * d, d}.  Positive multiples of 8 elements, row
+ *     stride >= d and <= 2^20; bases 16-byte aligned.  One block must hold page_size rows of every
+ *     head at these strides.
+ *   page_size: a positive multiple of 64 keys, so that a KV tile (64 keys, 32 at d = 256) lies
+ *     inside one page (other sizes: FA_ERR_UNSUPPORTED, the message names "page_size").
+ *   max_seqlen_k: an upper bound of the key counts; table_stride >= ceil(max_seqlen_k / page_size).
+ * Causal alignment (bottom-right), zero rows for rows that see no key, unwritten rows of no
+ * sequence, q_strides / o_strides, flags and the grid B * H * ceil(max_seqlen / 128) are
+ * fa_fwd_varlen_kv's.  The result is, bit for bit, fa_fwd_varlen_kv's on the cache gathered in
+ * table order (the same tiles in the same order; only addresses differ).
+ * Errors as fa_fwd_varlen for the shared arguments, and FA_ERR_INVALID_ARG for a null or misaligned
+ * block_table or seqused_k, num_blocks <= 0, page_size <= 0, max_seqlen_k <= 0, table_stride below
+ * ceil(max_seqlen_k / page_size), bad cache_strides.  total_tokens == 0 returns FA_OK without a
+ * launch.  fa_last_kernels: "fa_fwd_kernel<final, varlen, paged[, causal][, gqa]>" with its grid. */
+int fa_fwd_varlen_paged(const void* q, const void* k_cache, const void* v_cache, void* o,
+                        const int32_t* cu_seqlens, const int32_t* block_table, const int32_t* seqused_k,
+                        int64_t B, int64_t total_tokens, int64_t max_seqlen, int64_t max_seqlen_k,
+                        int64_t H, int64_t H_kv, int64_t d,
+                        int64_t num_blocks, int64_t page_size, int64_t table_stride,
+                        const int64_t* q_strides, const int64_t* cache_strides, const int64_t* o_strides,
+                        double softmax_scale, unsigned flags, int dtype, void* stream);
+/* Appends a chunk's new K / V rows to the paged pool fa_fwd_varlen_paged and fa_fwd_decode_paged
+ * read.  k_new and v_new are [total_tokens, H_kv, d] (new_strides: {token, head} shared by both, or
+ * NULL for contiguous, under fa_fwd_varlen's kv_strides rules); cu_seqlens / max_seqlen say which
+ * rows are sequence b's new tokens, clamped on the device exactly as fa_fwd_varlen clamps them
+ * (start_b, len_b above).  seqused_k[b] is the sequence's key count AFTER the append -- the array
+ * the attention call then takes -- so new token i of sequence b is logical key
+ *   p = seqused_k[b] - len_b + i
+ * and is copied to row p % page_size of block clamp(block_table[b * table_stride + p / page_size],
+ * 0, num_blocks - 1) of both pools.  A token with p < 0 or p >= max_seqlen_k (the keys the table
+ * maps; table_stride >= ceil(max_seqlen_k / page_size)) cannot be placed and is skipped.  Only rows
+ * that a token owns are written; nothing is read on the host; the copy runs on `stream`.
+ * d: any multiple of 8 up to 256 (else FA_ERR_UNSUPPORTED, "head dim"); FA_DTYPE_BF16 or
+ * FA_DTYPE_FP16.  Pool, table, page_size and cache_strides checks as fa_fwd_varlen_paged; the grid is
+ * B * ceil(max_seqlen / 32) * H_kv workgroups (those past a sequence's end exit) and must stay
+ * below 2^31.  total_tokens == 0 returns FA_OK without a launch.
+ * fa_last_kernels: "fa_kv_append_kernel" with its grid. */
+int fa_kv_append_paged(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                       const int32_t* cu_seqlens, const int32_t* block_table, const int32_t* seqused_k,
+                       int64_t B, int64_t total_tokens, int64_t max_seqlen, int64_t max_seqlen_k,
+                       int64_t H_kv, int64_t d,
+                       int64_t num_blocks, int64_t page_size, int64_t table_stride,
+                       const int64_t* new_strides, const int64_t* cache_strides, int dtype, void* stream);
 /* fa_fwd_v1_scaled on strided tensors.  q_strides, kv_strides (shared by k and v) and
  * o_strides each point to three element strides {batch, head, row} of a [B, H, L, d] view
  * whose d is contiguous -- e.g. a [B, L, H, d] tensor is {L*H*d, d, H*d} -- or are NULL for
